@@ -1,6 +1,19 @@
 """Train-step throughput of the AtmoNR Instant-NGP hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload nerf]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+                    [--workload nerf]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the workload's
+description). ``--dump-outputs DIR`` also writes ``.npy`` files. For the train step:
+``DIR/last_step/`` holds what the last timed step returned (loss, per-ray maps), which two
+runs of one build do not reproduce, and ``DIR/<name>.npy`` what the same step computes from
+the seeded initial state, forward arrays and gradients, which every run reproduces
+(probe_outputs). The nerf and extract workloads write their last timed step to ``DIR``;
+their runs reproduce it. Everything else described below -- the measured peaks,
+the per-kernel table and rooflines, the request counts, ``transient_window``, ``windows``,
+``alt_numerics``, ``strong_scaling`` and ``cpu_baseline`` -- takes runs of its own and is
+measured with ``--full`` only.
 
 Workload (BASELINE.json configs[2]): configs/instant_ngp.json with a 16-level T=2^19
 hash grid and 2x64 fused MLPs, B = 8192 rays x N = 1024 samples per rank per step, on a
@@ -64,6 +77,48 @@ _T0 = time.time()
 def say(msg: str) -> None:
     """Progress on stderr (rank 0's JSON line stays the only stdout line)."""
     print(f"[bench {time.time() - _T0:6.1f} s] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of an output larger than this
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``--dump-outputs``: write each tensor as ``path/<name>.npy`` (float32; float64 stays
+    float64). An output of more than DUMP_SAMPLE elements is written as a fixed sample of
+    that many of its flattened elements: sorted indices drawn by a generator seeded with 0,
+    so a given shape yields the same indices in every run and every build."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
+def step_outputs(loss, results=None) -> dict:
+    """What the caller of one train step receives: the loss and the per-ray maps its
+    forward returned. The parameters are state the step updates in place, not something
+    it returns: they are not dumped (nonfinite_params counts their health instead)."""
+    out = {"loss": loss}
+    for k in ("color_map_fine", "color_map_coarse", "color_map_atmo", "color_map_surf",
+              "color_surf"):
+        if results is not None and k in results:
+            out[k] = results[k]
+    return out
+
+
+def nonfinite_params(pipe) -> int:
+    """Parameter values that are NaN or infinite after the timed steps (result line). At
+    the flagship configuration the reference numerics' training (AdamW lr 1e-2, f16
+    gradients at loss scale 128) diverges between ~1,000 and ~1,500 steps after the settle:
+    the loss goes from 0.007 to 4.6 and NaNs appear in the density MLP and the hash table,
+    after which a step costs ~1.45 ms instead of ~1.8 ms because most of the backward has
+    nothing left to do. A run whose count is not 0 has timed that collapsed state."""
+    return int(sum((~torch.isfinite(p.detach())).sum() for p in pipe.parameters()).item())
 
 
 def measured_peaks(dev, spec: bool) -> dict:
@@ -338,7 +393,6 @@ def nerf_mlp_flops(net, n_rows: int) -> float:
 
 
 def run_nerf(args, ds, dev, rank, world, t_scene):
-    peaks = measured_peaks(dev, args.spec_peaks)
     """configs/nerf.json train step (nerf.py:179-240 + Adam, trainer.py:99-105): coarse
     64 stratified + fine 64+128 pdf samples per ray, two 8x256 AtmoNeRF MLPs (f32 library
     GEMMs), f32 composite, Adam. Batch 4096 rays per rank (nerf.json trainer.batch_size).
@@ -349,6 +403,7 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
     from atmonr_amd.parallel import FlatGradBucket
     from atmonr_amd.pipelines.factory import get_pipeline
 
+    peaks = measured_peaks(dev, args.spec_peaks) if args.full else None
     torch.manual_seed(0)
     if args.global_batch:
         if args.global_batch % world:
@@ -375,6 +430,8 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
             it = iter(loader)
             batch = next(it)
         res = pipe.forward(batch)
+        if last.get("keep"):  # --dump-outputs writes the last step's colour maps
+            last["results"] = res
         loss = pipe.compute_loss(batch, res)
         bucket.zero()
         loss.backward()
@@ -382,6 +439,7 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
         opt.step()
         return loss
 
+    last = {}
     for _ in range(args.warmup):
         loss = step()
     torch.cuda.synchronize()
@@ -389,7 +447,8 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.perf_counter()
-    for _ in range(args.steps):
+    for k in range(args.steps):
+        last["keep"] = bool(args.dump_outputs) and k == args.steps - 1
         loss = step()
     torch.cuda.synchronize()
     if world > 1:
@@ -401,6 +460,9 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(loss, last.get("results")))
+    last.clear()
     ms = elapsed / args.steps * 1e3
     value = batch_size * world * args.steps / elapsed
     nc, nf = NERF_CFG["sampler"]["N_c"], NERF_CFG["sampler"]["N_f"]
@@ -416,13 +478,14 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
                 "bound": "mfma", "achieved": round(tfs, 2), "peak": SPEC_PEAKS["mfma_f32_tfs"],
                 "unit": "TFLOP/s", "frac": round(tfs / SPEC_PEAKS["mfma_f32_tfs"], 4),
                 "ceiling": "f32 MFMA spec peak, MI355X_MICROARCH.md",
-                "measured_ceiling": {"peak": peaks["mfma_f32_tfs"],
-                                     "frac": round(tfs / peaks["mfma_f32_tfs"], 4)},
+                "measured_ceiling": None if peaks is None else {
+                    "peak": peaks["mfma_f32_tfs"],
+                    "frac": round(tfs / peaks["mfma_f32_tfs"], 4)},
                 "traffic": None,
                 "algorithmic_flops": flops, "units_per_launch": batch_size,
                 "flops_per_unit": flops / batch_size}
     kernels = None
-    if native and not args.no_kernel_timer:
+    if args.full and native and not args.no_kernel_timer:
         # untimed profiling pass: HIP events around every dense-layer launch (same stream)
         tags = {"nerf_linear_fwd", "nerf_linear_dx", "nerf_linear_dw"}
         prof_steps = 3
@@ -443,7 +506,7 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
                 "source": "HIP events around each nerf_linear_* launch, untimed pass of "
                           f"{prof_steps} steps; flops = the step's algorithmic MLP flops"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline
 
         cpu = cpu_baseline.run(budget_s=args.cpu_budget)
@@ -463,7 +526,7 @@ def run_nerf(args, ds, dev, rank, world, t_scene):
             "roofline": roofline, "cpu_baseline": cpu, "peaks": peaks,
             "kernels": kernels, "mlp": "native" if native else "library",
             "final_loss": round(final_loss, 6),
-            "scene_build_s": round(t_scene, 2)}), flush=True)
+            "scene_build_s": round(t_scene, 2), "full": args.full}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -482,7 +545,7 @@ def run_extract(args, ds, dev, rank, world, t_scene):
     from atmonr_amd.extract import GridExtractDataset
     from atmonr_amd.pipelines.instant_ngp import InstantNGPPipeline
 
-    peaks = measured_peaks(dev, args.spec_peaks)
+    peaks = measured_peaks(dev, args.spec_peaks) if args.full else None
     cfg = ingp_config(args.variant, args.samples)
     pipe = InstantNGPPipeline(cfg, ds, dtype=torch.float16, fused=True, seed=1337)
     pipe.send_tensors_to(dev)
@@ -507,19 +570,20 @@ def run_extract(args, ds, dev, rank, world, t_scene):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    prof = _lib.KernelTimer()
-    with prof:
-        for _ in range(args.profile_steps):
-            step()
-    kernels = {}
-    models = kernel_models(pipe, P)
-    models["field_fwd"] = dict(models["field_fwd"])
-    for name, st in sorted(prof.summary().items(), key=lambda kv: -kv[1]["total_ms"]):
-        e = {"avg_ms": round(st["avg_ms"], 4),
-             "ms_per_step": round(st["total_ms"] / args.profile_steps, 4)}
-        if name in models:
-            e.update(_roof(models[name], st["avg_ms"], peaks, "mfma_f16_tfs"))
-        kernels[name] = e
+    kernels, models = {}, {}
+    if args.full:  # untimed profiling pass: every kernel timed, the dominant one picked
+        prof = _lib.KernelTimer()
+        with prof:
+            for _ in range(args.profile_steps):
+                step()
+        models = kernel_models(pipe, P)
+        models["field_fwd"] = dict(models["field_fwd"])
+        for name, st in sorted(prof.summary().items(), key=lambda kv: -kv[1]["total_ms"]):
+            e = {"avg_ms": round(st["avg_ms"], 4),
+                 "ms_per_step": round(st["total_ms"] / args.profile_steps, 4)}
+            if name in models:
+                e.update(_roof(models[name], st["avg_ms"], peaks, "mfma_f16_tfs"))
+            kernels[name] = e
     dominant = next((n for n in kernels if "bound" in kernels[n]), None)
     torch.cuda.synchronize()
     if world > 1:
@@ -562,8 +626,11 @@ def run_extract(args, ds, dev, rank, world, t_scene):
                     "bytes_per_unit": mdl["bytes"] / P,
                     "ceiling": "HBM3E 8 TB/s, MI355X_MICROARCH.md" if r["bound"] == "hbm"
                     else "dense f16 MFMA spec peak, MI355X_MICROARCH.md"}
+    if args.dump_outputs and rank == 0:
+        # the extinction grid the loop filled (batches not reached in K steps stay zero)
+        dump_outputs(args.dump_outputs, {"sigma": sigma})
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline
 
         cpu = cpu_baseline.run_extract(budget_s=min(args.cpu_budget, 20.0))
@@ -583,7 +650,7 @@ def run_extract(args, ds, dev, rank, world, t_scene):
             "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels,
             "kernels_source": f"untimed profiling pass of {args.profile_steps} batches",
             "peaks": peaks, "sigma_checksum": float(sigma.double().sum().item()),
-            "scene_build_s": round(t_scene, 2)}), flush=True)
+            "scene_build_s": round(t_scene, 2), "full": args.full}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -671,6 +738,10 @@ class IngpJob:
             # MLP gradients reduce while the hash-grid backward runs
             bucket.enable_overlap()
         self.pipe, self.opt, self.bucket = pipe, opt, bucket
+        # --dump-outputs: an eager step leaves its forward results (keep_results) and the
+        # gradients of its backward (keep_grads) here
+        self.keep_results, self.last_results = False, None
+        self.keep_grads, self.last_grads = False, None
         self.set_batch(rank_batch, graph)
 
     def _after(self):
@@ -714,11 +785,19 @@ class IngpJob:
         idx = self.next_idx() if idx is None else idx
         batch = self.ds.__getbatch__(idx)
         res = self.pipe.forward(batch)
+        if self.keep_results:
+            self.last_results = res
         loss = self.pipe.compute_loss(batch, res)
         self.bucket.zero()
         loss.backward()
         if not self.sharded:
             self.bucket.all_reduce()
+        if self.keep_grads:  # the gradients the optimizer is about to read, by module
+            self.last_grads = {
+                n: torch.cat([p.grad.detach().reshape(-1)
+                              for p in getattr(self.pipe, n).parameters() if p.numel()])
+                for n in self.pipe.module_names
+                if any(p.numel() for p in getattr(self.pipe, n).parameters())}
         self.opt.step()  # ShardedAdam: reduce-scatter, sharded AdamW, all-gather
         return loss
 
@@ -775,6 +854,47 @@ class IngpJob:
         self.pipe = self.opt = self.bucket = None
 
 
+def probe_outputs(args, cfg, ds, dev, rank, world, rank_batch, numerics, shard) -> dict:
+    """``--dump-outputs``, the files of ``DIR`` itself: what the timed path's step computes
+    from a state every run reaches bit for bit, so that two builds can be compared array
+    by array. The last timed step (``DIR/last_step``) cannot serve for that: the hash-grid
+    backward sums its gradients with unordered f32 atomics (as tinycudann's), AdamW with
+    eps 1e-15 turns a last-bit difference of a near-zero gradient into a full lr-sized
+    update, and training amplifies that, so after the ~185 steps before the timed region
+    two runs of one build hold visibly different parameters (loss 0.00876 vs 0.00885, the
+    per-ray maps 0.17 apart in the mean). So, at the end of the run, the same step (a fresh
+    IngpJob of the run's numerics and shape, stepped eagerly) runs twice from the seeded
+    initial parameters on the loader's first two batches with re-seeded stratified draws:
+
+    * ``loss``, the four per-ray maps and the per-sample ``sigma_fine`` / ``color_fine`` (the
+      initial field is too thin to show in the maps): the first step's forward, i.e. the
+      sampler, hash-grid, field, composite and loss forward kernels;
+    * ``grad_<module>``: every module's parameter gradient as the first step's backward
+      leaves it, before AdamW reads it (reference numerics: the f32 sums before tcnn's f16
+      rounding, which the update applies). These carry the magnitudes the loss, composite,
+      field, MLP and hash-grid backward kernels produce; the hash grids' sums differ from
+      run to run in the last f32 bits only (the atomics' order);
+    * ``step2_*`` (loss and maps): the second step's forward after the first AdamW update.
+      With zero moments that update is lr * sign(g), and it leaves the default numerics'
+      field dead (warm_start), so these show little more than that AdamW ran."""
+    torch.manual_seed(0)
+    probe = IngpJob(args, cfg, ds, dev, rank, world, rank_batch, numerics, False, shard, None)
+    probe.keep_results = True
+    out = {}
+    for prefix in ("", "step2_"):
+        probe.keep_grads = not prefix
+        loss = probe.eager_step()
+        for k, v in step_outputs(loss, probe.last_results).items():
+            out[prefix + k] = v.detach().clone()
+        if not prefix:
+            for k in ("sigma_fine", "color_fine"):
+                out[k] = probe.last_results[k].detach().clone()
+            out.update({f"grad_{n}": g for n, g in probe.last_grads.items()})
+    torch.cuda.synchronize()
+    probe.release()
+    return out
+
+
 def _launch_ranks(n: int) -> int:
     """torch.distributed.run with N local ranks on this script (same arguments), as a
     child process: rendezvous on 127.0.0.1, one process per GPU."""
@@ -800,6 +920,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10,
                     help="untimed steps first (the bench network's first AdamW steps kill its "
                          "densities; it is alive again from step ~7: tools/liveness.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (DIR/last_step/<name>.npy) and "
+                         "the step's outputs and gradients from the seeded initial state "
+                         "(DIR/<name>.npy), rank 0; probe_outputs, dump_outputs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: peaks, the "
+                         "per-kernel table and rooflines, request counts, the transient "
+                         "window, the other numerics, strong scaling, the CPU baseline")
     ap.add_argument("--batch", type=int, default=8192,
                     help="rays per rank per step (weak scaling, the default)")
     ap.add_argument("--global-batch", type=int, default=0,
@@ -869,6 +997,8 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=3,
                     help="untimed steps with every kernel timed (per-kernel breakdown)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -915,6 +1045,7 @@ def main():
     else:
         rank_batch, scaling = args.batch, "weak"
     cfg = ingp_config(args.variant, args.samples)
+    torch.manual_seed(0)  # the stratified draws: the same inputs in every run
     occ = None
     if args.occupancy:
         from atmonr_amd.occupancy import OccupancyGrid
@@ -945,21 +1076,22 @@ def main():
         # transient: over the next ~100 steps the loss falls 0.07 -> 0.01 and the nonzero
         # share of dL/denc rows from ~0.65 to ~0.25 (profiles/r05_liveness_ref400.log),
         # then stays there for the rest of training. The timed steps run after
-        # ``--settle`` reference-numerics steps; the first K of them are timed here too and
-        # reported as ``transient_window`` (one rank).
+        # ``--settle`` reference-numerics steps, whatever K is; with --full the first
+        # min(K, settle) of them are timed here too and reported as ``transient_window``
+        # (one rank).
         done = 0
-        if world == 1:
+        if world == 1 and args.full:
+            done = min(args.steps, args.settle)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
+            for _ in range(done):
                 step()
             torch.cuda.synchronize()
             el = time.perf_counter() - t0
-            done = args.steps
-            transient = {"steps_after_warm_start": [0, args.steps],
-                         "value": round(rank_batch * args.steps / el, 1),
-                         "ms_per_step": round(el / args.steps * 1e3, 3)}
-        for _ in range(max(0, args.settle - done)):
+            transient = {"steps_after_warm_start": [0, done],
+                         "value": round(rank_batch * done / el, 1),
+                         "ms_per_step": round(el / done * 1e3, 3)}
+        for _ in range(args.settle - done):
             step()
         warm["settle_steps"] = args.settle
         warm["settle_numerics"] = numerics
@@ -974,51 +1106,56 @@ def main():
     # Untimed profiling pass: HIP events around every libanr call give the per-kernel
     # breakdown and pick the dominant kernel; the timed region below then brackets only
     # that kernel's launches (events around every call would cost ~0.2 ms per step). A
-    # graphed job profiles its eager form (the same kernels and arguments).
+    # graphed job profiles its eager form (the same kernels and arguments). --full only: a
+    # plain run goes from the warm-up straight to the timed steps.
     M = rank_batch * args.samples
-    say("warm-up done; measuring peaks")
-    peaks = measured_peaks(dev, args.spec_peaks)
     mfma_key = {"f32": "mfma_f32_tfs", "bf16": "mfma_bf16_tfs"}.get(args.dtype, "mfma_f16_tfs")
-    pmc = {}
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_path):
-        try:
-            pmc = json.load(open(pmc_path))
-        except (OSError, ValueError):
-            pmc = {}
-    pmc_sfx = (f"{args.variant}{'' if args.dtype == 'f16' else '-' + args.dtype}:"
-               f"{rank_batch}x{args.samples}")
-    req = count_hash_requests(job, args.samples) if occ is None else None
-    nreq = None if req is None else req[0]
-    models = kernel_models(pipe, M, pmc, pmc_sfx, requests=nreq,
-                           nz_rows=None if req is None else req[2],
-                           dir_tiles=None if req is None else req[3])
-    kernels, dominant = {}, None
-    if not args.no_kernel_timer:
-        kernels = job.profile(args.profile_steps, models, peaks, mfma_key)
-        dominant = next((n for n in kernels if "bound" in kernels[n]
-                         and not kernels[n].get("overlapped")), None)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
+    peaks, pmc, pmc_sfx, req, models, kernels, dominant = None, {}, "", None, {}, {}, None
+    if args.full:
+        say("warm-up done; measuring peaks")
+        peaks = measured_peaks(dev, args.spec_peaks)
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(pmc_path):
+            try:
+                pmc = json.load(open(pmc_path))
+            except (OSError, ValueError):
+                pmc = {}
+        pmc_sfx = (f"{args.variant}{'' if args.dtype == 'f16' else '-' + args.dtype}:"
+                   f"{rank_batch}x{args.samples}")
+        req = count_hash_requests(job, args.samples) if occ is None else None
+        nreq = None if req is None else req[0]
+        models = kernel_models(pipe, M, pmc, pmc_sfx, requests=nreq,
+                               nz_rows=None if req is None else req[2],
+                               dir_tiles=None if req is None else req[3])
+        if not args.no_kernel_timer:
+            kernels = job.profile(args.profile_steps, models, peaks, mfma_key)
+            dominant = next((n for n in kernels if "bound" in kernels[n]
+                             and not kernels[n].get("overlapped")), None)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
 
     # graphed steps cannot carry events per launch: their dominant kernel is timed by
     # job.time_dominant after the timed region (events recorded inside the graph)
     timer = _lib.KernelTimer(only={dominant}) if dominant and not job.graphed else None
     # two windows of the timed steps (GPU events at the start, after K // 2 steps and at
     # the end, on the compute stream): the reference numerics' field keeps learning
-    # through the timed steps, so the step cost can drift between the halves
-    win = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    # through the timed steps, so the step cost can drift between the halves (--full)
+    win = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if args.full else None
     half = args.steps // 2
+    last = args.steps - 1 if args.dump_outputs else -1
     t_start = time.perf_counter()
-    win[0].record()
+    if win:
+        win[0].record()
     with (timer if timer else _NullCtx()):
         for k in range(args.steps):
-            if k == half:
+            if win and k == half:
                 win[1].record()
+            job.keep_results = k == last  # --dump-outputs: the last step's forward results
             loss = step()
-    win[2].record()
+    if win:
+        win[2].record()
     t_host = time.perf_counter() - t_start  # host time to issue the K steps (no waits)
     torch.cuda.synchronize()
     if world > 1:
@@ -1032,8 +1169,19 @@ def main():
     final_loss = float(loss.item())
 
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (a graphed step: the loss alone). Kept apart
+        # from the files of DIR itself because two runs of one build differ in it by far
+        # more than rounding (probe_outputs)
+        dump_outputs(os.path.join(args.dump_outputs, "last_step"),
+                     step_outputs(loss, job.last_results))
+    job.keep_results, job.last_results = False, None
+    bad_params = nonfinite_params(pipe)
+    if bad_params:
+        say(f"{bad_params} non-finite parameter values after the timed steps: the training "
+            "has diverged, the timed steps ran a collapsed field (nonfinite_params)")
     windows = None
-    if 0 < half < args.steps:
+    if win and 0 < half < args.steps:
         windows = {"steps": [half, args.steps - half],
                    "ms_per_step": [round(win[0].elapsed_time(win[1]) / half, 4),
                                    round(win[1].elapsed_time(win[2]) / (args.steps - half), 4)],
@@ -1070,7 +1218,8 @@ def main():
                 round(req[3], 4), round(req2[3], 4)]
 
     strong = None
-    if world > 1 and scaling == "weak" and not args.no_strong and args.batch % world == 0:
+    if (args.full and world > 1 and scaling == "weak" and not args.no_strong
+            and args.batch % world == 0):
         # the same job at a fixed global batch of --batch rays (SURVEY §8(e)'s strong-
         # scaling target), timed the same way after a short warm-up at the new shape
         sb = args.batch // world
@@ -1098,7 +1247,8 @@ def main():
     # reference's f16 composite / loss / loss-scaled backward (numerics="reference", the
     # PSNR-parity path) beside the build numerics, or the other way round
     alt = None
-    if world == 1 and not args.no_alt_numerics and occ is None and args.dtype == "f16":
+    if (args.full and world == 1 and not args.no_alt_numerics and occ is None
+            and args.dtype == "f16"):
         other = "reference" if numerics == "build" else "build"
         del step
         job.release()
@@ -1207,11 +1357,17 @@ def main():
                     ent["bytes"] / (st["avg_ms"] * 1e-3) / 1e9 / peaks["hbm_copy_gbs"], 4)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline
 
         say("CPU baseline (oracle, configs/nerf.json step)")
         cpu = cpu_baseline.run(budget_s=args.cpu_budget)
+
+    if args.dump_outputs:
+        # last of all: the probe re-seeds the generator, which no measured leg may see
+        outs = probe_outputs(args, cfg, ds, dev, rank, world, rank_batch, numerics, shard)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
 
     if rank == 0:
         T = 2 ** cfg["instant_ngp"]["encoding"]["log2_hashmap_size"]
@@ -1282,8 +1438,16 @@ def main():
                 "kept_fraction_last_step": round(occ.last_fraction, 4),
                 "occupied_cells": round(occ.occupancy_fraction(), 4)},
             "final_loss": round(final_loss, 6),
+            "nonfinite_params": bad_params,
             "scene_build_s": round(t_scene, 2),
+            "full": args.full,
         }
+        if not args.full:  # measured by runs of their own, with --full only
+            for k in ("windows", "transient_window", "d_enc_nonzero_frac",
+                      "d_enc_nonzero_rows_frac", "d_color_nonzero_tiles_frac", "roofline",
+                      "roofline_targets", "cpu_baseline", "strong_scaling", "alt_numerics",
+                      "peaks", "kernels", "kernels_source"):
+                del line[k]
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

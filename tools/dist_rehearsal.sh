@@ -10,8 +10,8 @@ for mode in overlap plain; do
   [ "$mode" = plain ] && extra="--no-overlap"
   timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 \
-    --no-cpu-baseline --no-kernel-timer $extra > "$OUT/b2_$mode.log" 2>&1 || exit $?
+    --full --no-cpu-baseline --no-kernel-timer $extra > "$OUT/b2_$mode.log" 2>&1 || exit $?
 done
 unset ANR_DIST_BACKEND
-timeout -k 10 300 python -u bench.py > "$OUT/b1.log" 2>&1 || exit $?
+timeout -k 10 300 python -u bench.py --full > "$OUT/b1.log" 2>&1 || exit $?
 echo done

@@ -244,6 +244,11 @@ _SIGNATURES = {
         [POINTER(MlpDesc), POINTER(MlpDesc), c_int32, _P, _P, c_int64, _P, c_int64, c_int64,
          _P, _P, c_int64, _P],
     ),
+    "anr_ingp_field_fwd_h": (
+        c_int32,
+        [POINTER(MlpDesc), POINTER(MlpDesc), c_int32, _P, _P, c_int64, _P, c_int64, c_int64,
+         _P, _P, c_int64, _P],
+    ),
     "anr_ingp_hash_field_fwd": (
         c_int32,
         [POINTER(HashGridDesc), _P, c_int64, _P, c_int32, _P, c_int64, POINTER(MlpDesc),
@@ -314,6 +319,11 @@ _SIGNATURES = {
          c_int64, _P, c_int64, _P, _P, c_float, _P, _P],
     ),
     "anr_ingp_field_bwd_ref16_rows": (
+        c_int32,
+        [POINTER(MlpDesc), POINTER(MlpDesc), _P, _P, c_int64, _P, c_int64, c_int64, _P, _P,
+         c_int64, _P, c_int64, _P, _P, c_float, _P, _P, c_int64, _P],
+    ),
+    "anr_ingp_field_bwd_ref16_rows_h": (
         c_int32,
         [POINTER(MlpDesc), POINTER(MlpDesc), _P, _P, c_int64, _P, c_int64, c_int64, _P, _P,
          c_int64, _P, c_int64, _P, _P, c_float, _P, _P, c_int64, _P],

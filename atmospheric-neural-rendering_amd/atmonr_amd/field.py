@@ -25,6 +25,11 @@ only dL/denc. The weights are packed into MFMA fragment order once per forward. 
 networks (BASELINE configs[4]: f16 hash features, bf16 MFMA MLP) run only this way.
 The backward's workspace (per-wavefront f16 gradient maxima) is allocated here, through
 torch's caching allocator, at anr_ingp_field_bwd_workspace_bytes.
+
+Reference numerics (pipe.numerics == "reference") are the exception to "f32 across kernel
+boundaries": sigma, colour and their gradients are tcnn's f16 values there, and the
+two-kernel forward and the f16-rows backward carry them as f16 (anr_ingp_field_fwd_h,
+anr_ingp_field_bwd_ref16_rows_h; ANR_REF_F16_IO=0 carries the same values as f32).
 """
 
 from __future__ import annotations
@@ -117,7 +122,17 @@ class IngpFieldFn(torch.autograd.Function):
                  tag="hash_fwd")
         ctx.enc_ld = enc_ld
         if fused:
-            if rows is None:
+            if rows is None and _REF_F16_IO and getattr(pipe, "numerics", None) == "reference":
+                # reference numerics: sigma and colour leave as tcnn's f16 outputs, the values
+                # the f16 composite rounded the f32 outputs to as it loaded them; its f16
+                # gradients then come back to the backward as they are (anr_..._rows_h).
+                # ANR_REF_F16_IO=0: the f32 interchange (A/B)
+                sigma = torch.empty(M, device=dev, dtype=torch.float16)
+                color = torch.empty(M, nb, device=dev, dtype=torch.float16)
+                call("anr_ingp_field_fwd_h", pdesc, ddesc, mma, ptr(packed), ptr(enc), enc_ld,
+                     ptr(dirs), n_per_ray, M, ptr(sigma), ptr(color), color.stride(0), s,
+                     tag="field_fwd")
+            elif rows is None:
                 sigma = torch.empty(M, device=dev, dtype=torch.float32)
                 color = torch.empty(M, nb, device=dev, dtype=torch.float32)
                 call("anr_ingp_field_fwd", pdesc, ddesc, mma, ptr(packed), ptr(enc), enc_ld,
@@ -197,14 +212,23 @@ class IngpFieldFn(torch.autograd.Function):
         g_dir, direct_d = _grad_target(p_dir, dev)
         if d_color is None:
             d_color = torch.zeros(M, pipe.dir_mlp.n_output_dims, device=dev)
-        d_color = d_color.float().contiguous()
-        d_sigma = d_sigma.float().contiguous() if d_sigma is not None else None
         n_enc = pipe.pos_encoder.hash_grids[0].n_out
+        ls = getattr(pipe, "loss_scale", None)
+        rows_form = bool(ls and _ROW_BITS and not _TILE_SKIP and n_enc == 32 and ctx.rows is None)
+        # f16 gradients (the f16 composite backward's outputs) go to the f16-rows backward
+        # as they are; every other form reads f32
+        half_grads = (rows_form and d_color.dtype == torch.float16
+                      and (d_sigma is None or d_sigma.dtype == torch.float16))
+        if half_grads:
+            d_color = d_color.contiguous()
+            d_sigma = d_sigma.contiguous() if d_sigma is not None else None
+        else:
+            d_color = d_color.float().contiguous()
+            d_sigma = d_sigma.float().contiguous() if d_sigma is not None else None
         pdesc, ddesc = ctypes.byref(pipe.pos_mlp.desc), ctypes.byref(pipe.dir_mlp.desc)
         mma = _mma_code(pipe)
-        ls = getattr(pipe, "loss_scale", None)
         tiles = row_nz = None
-        if ls and _ROW_BITS and not _TILE_SKIP and n_enc == 32 and ctx.rows is None:
+        if rows_form:
             # reference numerics (default since r06): dL/denc as f16 rows, the values
             # tinycudann hands the hash grid (exactly f16 numbers), plus one bit per row with
             # a nonzero value; the hash-grid backward loads and walks only those rows
@@ -217,7 +241,8 @@ class IngpFieldFn(torch.autograd.Function):
             # SIMD, and a full pass over the tiles it lists. ANR_POS_PASS=0: one kernel
             ws_bytes = _lib.load().anr_ingp_field_bwd_ref16_rows_workspace_bytes(M) if _POS_PASS else 0
             ws = torch.empty(max(1, ws_bytes), device=dev, dtype=torch.uint8) if ws_bytes else None
-            call("anr_ingp_field_bwd_ref16_rows", pdesc, ddesc, ptr(packed), ptr(enc),
+            call("anr_ingp_field_bwd_ref16_rows_h" if half_grads
+                 else "anr_ingp_field_bwd_ref16_rows", pdesc, ddesc, ptr(packed), ptr(enc),
                  ctx.enc_ld, ptr(dirs), ctx.n_per_ray, M, ptr(d_sigma), ptr(d_color),
                  d_color.stride(0), ptr(d_enc), d_enc.stride(0), ptr(g_pos), ptr(g_dir),
                  float(ls), ptr(row_nz), None if ws is None else ptr(ws), ws_bytes, s,
@@ -306,6 +331,9 @@ _HASH_FIELD = os.environ.get("ANR_HASH_FIELD", "0") != "0"
 _TILE_SKIP = os.environ.get("ANR_TILE_SKIP", "0") != "0"
 _ROW_BITS = os.environ.get("ANR_ROW_BITS", "1") != "0"
 _POS_PASS = os.environ.get("ANR_POS_PASS", "1") != "0"
+# reference numerics: f16 sigma / colour out of the two-kernel field forward and f16
+# gradients into its backward (0: the f32 interchange through the f32 entry points, A/B)
+_REF_F16_IO = os.environ.get("ANR_REF_F16_IO", "1") != "0"
 
 
 def field_fused(pipe) -> bool:

@@ -96,8 +96,11 @@ class _CompositeRef16Fn(torch.autograd.Function):
         surf = torch.empty(B, C, device=dev, dtype=f16) if cs is not None else None
         weights = torch.empty(B, N, 1, device=dev, dtype=f16)
         alpha = torch.empty(B, N, 1, device=dev, dtype=f16)
-        c16 = torch.empty(B, N, C, device=dev, dtype=f16) if want16 else None
-        s16 = torch.empty(B, N, 1, device=dev, dtype=f16) if want16 else None
+        # f16 inputs hold the f16 values already: no copies are written, the inputs themselves
+        # are saved for the backward and returned as the f16 colour / density results
+        copies = want16 and color.dtype != f16
+        c16 = torch.empty(B, N, C, device=dev, dtype=f16) if copies else None
+        s16 = torch.empty(B, N, 1, device=dev, dtype=f16) if copies else None
         call("anr_composite_ref16_fwd", ptr(zc), float(z_scale), ptr(color), ptr(sigma), ptr(cs),
              dtype_code(color.dtype), B, N, C, ptr(cm), ptr(atmo), ptr(surf), ptr(weights),
              ptr(alpha), ptr(c16), ptr(s16), _lib.stream(dev), tag="composite_fwd")
@@ -105,10 +108,12 @@ class _CompositeRef16Fn(torch.autograd.Function):
         # hand it reads those (half the bytes of f32 inputs) and still returns gradients in
         # the inputs' dtype
         ctx.out_dtype = color.dtype
-        if want16:
+        if copies:
             ctx.save_for_backward(zc, c16, s16, cs)
         else:
             ctx.save_for_backward(zc, color, sigma, cs)
+            if want16:
+                c16, s16 = color.detach(), sigma.detach()
         ctx.set_materialize_grads(False)
         ctx.z_scale = float(z_scale)
         ctx.zero_rays = zero_rays
@@ -153,7 +158,9 @@ def render_with_surface_ref16(z_vals, color, sigma, color_surf, z_scale: float =
     counts rays whose alpha rounded to exactly 1 in f16 (torch's zero-input backward
     branch, not reproduced: those rays get zero gradients). ``inputs_f16``: also return
     color and sigma rounded to f16 as the kernel reads them (tcnn's f16 outputs, which the
-    reference's forward returns), written by the same kernel."""
+    reference's forward returns), written by the same kernel; f16 color / sigma are returned
+    as they are (no copy). f16 inputs also get f16 gradients, and the backward then parks its
+    two scratch values per sample as one 4-byte pair (csrc/ref16.hip)."""
     _check(z_vals, color, sigma)
     if zero_rays is None:
         zero_rays = torch.zeros(1, dtype=torch.int32, device=color.device)

@@ -92,7 +92,8 @@ class InstantNGPPipeline(Pipeline):
         ingp = self.config["instant_ngp"]
         nb = self.config["num_bands"]
         # the fused path keeps activations / gradients in f32 (build numerics); tcnn's f16
-        # outputs in reference numerics
+        # outputs in reference numerics: the per-ray surface modules here, and the fused
+        # field's sigma / colour and their gradients (field.py, ANR_REF_F16_IO)
         fdt = torch.float32 if fused and numerics == "build" else None
         self.pos_encoder = Encoding(3, ingp["encoding"], seed=seed, dtype=dtype)
         self.pos_mlp = Network(self.pos_encoder.n_output_dims, 16, ingp["network"],
@@ -239,7 +240,8 @@ class InstantNGPPipeline(Pipeline):
         if self.numerics == "reference":
             if self._zero_rays is None:  # counts over the pipeline's life (no per-step op)
                 self._zero_rays = torch.zeros(1, dtype=torch.int32, device=color.device)
-            # the kernel also writes tcnn's f16 colour / density outputs for the results
+            # the results hold tcnn's f16 colour / density outputs: the field's own f16 outputs,
+            # or (f32 field outputs: ANR_HASH_FIELD=1, ANR_REF_F16_IO=0) copies the kernel writes
             color_map, _, weights, atmo, surf, color, sigma = render_with_surface_ref16(
                 z_vals, color, sigma, color_surf, z_scale=self.scale / 1000,
                 zero_rays=self._zero_rays, inputs_f16=True)

@@ -287,6 +287,15 @@ struct Args {
   // its pos / list passes (workspace): the tiles with a nonzero dL/dcolor and their count
   int32_t* tile_list;
   uint32_t* tile_count;
+  // the reference-numerics f16 interchange with the f16 composite (element strides as
+  // above). anr_ingp_field_fwd_h: sigma / colour stored as f16, the f32 value the f32
+  // kernel stores rounded to nearest even (instead of sigma / color);
+  // anr_ingp_field_bwd_ref16_rows_h: dL/dsigma / dL/dcolor read as f16 (instead of
+  // d_sigma / d_color; f16 -> f32 is exact, so the arithmetic after the load is the same)
+  _Float16* sigma_h;
+  _Float16* color_h;
+  const _Float16* d_sigma_h;
+  const _Float16* d_color_h;
 };
 
 // ROWS is a compile-time choice: a run-time test on a.rows in the prefetch paths put a
@@ -381,7 +390,7 @@ struct Rows {
   float ds;       // dL/dsigma[row] (backward, g == 0 lanes)
 };
 
-template <bool ROWS>
+template <bool ROWS, bool HG = false>
 __device__ __forceinline__ void load_rows(const Args& a, int64_t row, int g, bool bwd, Rows& in) {
   in.xe = h8{};
   in.dx = in.dy = in.dz = 0.0f;
@@ -396,9 +405,25 @@ __device__ __forceinline__ void load_rows(const Args& a, int64_t row, int g, boo
     in.dx = d[0] * 2.0f - 1.0f;
     in.dy = d[1] * 2.0f - 1.0f;
     in.dz = d[2] * 2.0f - 1.0f;
-    if (bwd && a.d_sigma) in.ds = a.d_sigma[drow];
+    if constexpr (HG) {
+      if (bwd && a.d_sigma_h) in.ds = static_cast<float>(a.d_sigma_h[drow]);
+    } else {
+      if (bwd && a.d_sigma) in.ds = a.d_sigma[drow];
+    }
   }
-  if (bwd) {
+  if constexpr (HG) {
+    if (bwd) {  // 8 B per row where the f32 form loads 16
+      const int c0 = 4 * g;
+      const _Float16* dcp = a.d_color_h + drow * a.d_color_stride + c0;
+      if (c0 + 3 < a.n_out && (a.d_color_stride & 3) == 0) {
+        in.dc = __builtin_convertvector(*reinterpret_cast<const h4*>(dcp), f4);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (c0 + i < a.n_out) in.dc[i] = static_cast<float>(dcp[i]);
+      }
+    }
+  } else if (bwd) {
     const int c0 = 4 * g;
     const float* dcp = a.d_color + drow * a.d_color_stride + c0;
     if (c0 + 3 < a.n_out && (a.d_color_stride & 3) == 0) {
@@ -617,6 +642,7 @@ __device__ __forceinline__ void fwd_raw_to_rows(const FwdRaw& r, Rows& in) {
 // remap made the compiler wait with vmcnt(0) twice per tile: one store round trip and
 // one prefetch round trip per tile.
 typedef uint32_t u4v __attribute__((vector_size(16)));
+typedef uint32_t u2v __attribute__((vector_size(8)));
 typedef __attribute__((address_space(4))) const float const_f32;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(const void* p, int64_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, static_cast<int>(bytes),
@@ -627,9 +653,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(const void* p, int64_
 // (3 waves); capped at 128 it fits in 126 without spills, and the fourth wave hides more
 // of the per-tile prefetch latency (field fwd 0.204 -> 0.201 ms, step -0.02 ms;
 // profiles/r03_field_fwd_occ.log). The grid is sized from the same occupancy query.
-template <int W, int NHD, bool ROWS, bool BF, bool UT>
+//
+// HO (anr_ingp_field_fwd_h): the same values stored as f16 -- a.sigma_h / a.color_h, each
+// the f32 value of the f32 form rounded to nearest even after its max(., 0). The
+// uniform-tile form keeps its shape: one 2-byte sigma and one 8-byte colour buffer store
+// per lane and tile, and the same two dropped stores ahead of the loop.
+template <int W, int NHD, bool ROWS, bool BF, bool UT, bool HO = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) fwd_kernel(Args a) {
   static_assert(!(UT && ROWS), "the uniform-tile form needs dense rows");
+  static_assert(!(HO && ROWS), "f16 outputs: dense rows only");
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   // wave index through readfirstlane: the tile loop then runs on scalar registers
   const int waves = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -642,8 +674,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
   auto store = [&](const Tile<W, NHD>& t, int64_t row) {
     if (row < a.M) {
       const int64_t drow = dense_row<ROWS>(a, row);
-      if (g == 0) a.sigma[drow] = fmaxf(t.po[0], 0.0f);
       const int c0 = 4 * g;
+      if constexpr (HO) {
+        if (g == 0) a.sigma_h[drow] = static_cast<_Float16>(fmaxf(t.po[0], 0.0f));
+        _Float16* cp = a.color_h + drow * a.color_stride + c0;
+        if (c0 + 3 < a.n_out && (a.color_stride & 3) == 0) {
+          f4 v;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] = fmaxf(t.col[i], 0.0f);
+          *reinterpret_cast<h4*>(cp) = to_h4<false>(v);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (c0 + i < a.n_out) cp[i] = static_cast<_Float16>(fmaxf(t.col[i], 0.0f));
+        }
+        return;
+      }
+      if (g == 0) a.sigma[drow] = fmaxf(t.po[0], 0.0f);
       if (c0 + 3 < a.n_out && (a.color_stride & 3) == 0) {
         f4 v;
 #pragma unroll
@@ -663,9 +710,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
     store(t, row);
   };
   if constexpr (UT) {
-    const __amdgpu_buffer_rsrc_t rsig = out_rsrc(a.sigma, a.M * 4);
-    const __amdgpu_buffer_rsrc_t rcol = out_rsrc(a.color, a.M * a.color_stride * 4);
-    const uint32_t cs_bytes = static_cast<uint32_t>(a.color_stride) * 4u;
+    constexpr uint32_t ES = HO ? 2u : 4u;  // bytes per output element
+    const __amdgpu_buffer_rsrc_t rsig =
+        HO ? out_rsrc(a.sigma_h, a.M * ES) : out_rsrc(a.sigma, a.M * ES);
+    const __amdgpu_buffer_rsrc_t rcol = HO ? out_rsrc(a.color_h, a.M * a.color_stride * ES)
+                                           : out_rsrc(a.color, a.M * a.color_stride * ES);
+    const uint32_t cs_bytes = static_cast<uint32_t>(a.color_stride) * ES;
     auto enc_ptr = [&](int64_t t) {
       return reinterpret_cast<const h8*>(a.enc + (t * 16 + li) * a.enc_stride + g * a.enc_gstride);
     };
@@ -674,8 +724,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
       nxe = *enc_ptr(tile);
       // two dropped stores: the loop is entered with the vector-memory queue of its back
       // edge (an input load, then a tile's two stores)
-      __builtin_amdgcn_raw_buffer_store_b32(0u, rsig, 0x80000000u, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{0u, 0u, 0u, 0u}, rcol, 0x80000000u, 0, 0);
+      if constexpr (HO) {
+        __builtin_amdgcn_raw_buffer_store_b16(uint16_t{0}, rsig, 0x80000000u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(u2v{0u, 0u}, rcol, 0x80000000u, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_buffer_store_b32(0u, rsig, 0x80000000u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(u4v{0u, 0u, 0u, 0u}, rcol, 0x80000000u, 0, 0);
+      }
     }
     for (; tile < n_full; tile += tstride) {
       Rows cur;
@@ -699,8 +754,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
       const bool valid = true;
       tile_forward<W, NHD, 1, BF>(fw, &cur, &valid, g, &t, NoSink{});
       const uint32_t row = static_cast<uint32_t>(tile * 16 + li);
-      const uint32_t so = g == 0 ? row * 4u : 0x80000000u;
+      const uint32_t so = g == 0 ? row * ES : 0x80000000u;
       const uint32_t co = g == 0 ? row * cs_bytes : 0x80000000u;
+      if constexpr (HO) {
+        const _Float16 sh = static_cast<_Float16>(fmaxf(t.po[0], 0.0f));
+        __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, sh), rsig, so, 0, 0);
+        const f4 cv = {fmaxf(t.col[0], 0.0f), fmaxf(t.col[1], 0.0f), fmaxf(t.col[2], 0.0f),
+                       fmaxf(t.col[3], 0.0f)};
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, to_h4<false>(cv)), rcol, co,
+                                              0, 0);
+        continue;
+      }
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(t.po[0], 0.0f)), rsig, so, 0, 0);
       const u4v v = {__float_as_uint(fmaxf(t.col[0], 0.0f)), __float_as_uint(fmaxf(t.col[1], 0.0f)),
                      __float_as_uint(fmaxf(t.col[2], 0.0f)), __float_as_uint(fmaxf(t.col[3], 0.0f))};
@@ -963,14 +1027,19 @@ __global__ void __launch_bounds__(1024) absmax_kernel(Args a, int64_t rows_per_w
 // on the loaded values here — any use would make the compiler wait for the load right
 // away; raw_to_rows() converts them one tile later. Every lane loads its row's direction,
 // d_sigma and d_color (same addresses across the lane groups: no extra traffic).
-struct RawRows {
+// HG (f16 gradients, a.d_sigma_h / a.d_color_h): the row's dL/dcolor is one 8-byte load and
+// its dL/dsigma a 2-byte load (zero-extended into a 32-bit register), converted to f32 --
+// exactly -- by raw_to_rows() like the rest.
+template <bool HG>
+struct RawRowsT {
   h8 xe;
-  float d0, d1, d2, ds;
-  f4 dc;
+  float d0, d1, d2;
+  typename std::conditional<HG, uint32_t, float>::type ds;
+  typename std::conditional<HG, h4, f4>::type dc;
 };
 
-template <bool ROWS>
-__device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawRows& r) {
+template <bool ROWS, bool HG>
+__device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawRowsT<HG>& r) {
   r.xe = *reinterpret_cast<const h8*>(a.enc + row * a.enc_stride + g * a.enc_gstride);
   const int64_t drow = dense_row<ROWS>(a, row);
   const uint32_t ray = static_cast<uint32_t>(drow) / a.n_per_ray;
@@ -978,18 +1047,29 @@ __device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawR
   r.d0 = d[0];
   r.d1 = d[1];
   r.d2 = d[2];
-  r.ds = a.d_sigma[drow];
-  r.dc = *reinterpret_cast<const f4*>(a.d_color + drow * a.d_color_stride);
+  if constexpr (HG) {
+    r.ds = reinterpret_cast<const uint16_t*>(a.d_sigma_h)[drow];
+    r.dc = *reinterpret_cast<const h4*>(a.d_color_h + drow * a.d_color_stride);
+  } else {
+    r.ds = a.d_sigma[drow];
+    r.dc = *reinterpret_cast<const f4*>(a.d_color + drow * a.d_color_stride);
+  }
 }
 
-__device__ __forceinline__ void raw_to_rows(const RawRows& r, int g, Rows& in) {
+template <bool HG>
+__device__ __forceinline__ void raw_to_rows(const RawRowsT<HG>& r, int g, Rows& in) {
   in.xe = r.xe;
   in.dx = r.d0 * 2.0f - 1.0f;
   in.dy = r.d1 * 2.0f - 1.0f;
   in.dz = r.d2 * 2.0f - 1.0f;
-  in.ds = r.ds;
   const f4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
-  in.dc = g == 0 ? r.dc : z4;
+  if constexpr (HG) {
+    in.ds = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(r.ds)));
+    in.dc = g == 0 ? __builtin_convertvector(r.dc, f4) : z4;
+  } else {
+    in.ds = r.ds;
+    in.dc = g == 0 ? r.dc : z4;
+  }
 }
 
 // ---------------------------------------------------------------------------------
@@ -1054,10 +1134,15 @@ __device__ __forceinline__ h4 tr_b(h8 x, h8 sel) {
 // SIMD -- while a tile with a nonzero dL/dcolor is appended to a.tile_list (a.tile_count)
 // and left alone. REF 3 (the list pass, launched after it): REF 2 on exactly the listed
 // tiles (count read on the device), the whole network.
-template <int W, int NHD, bool FAST, bool ROWS, bool BF, int REF = 0>
+// HG (anr_ingp_field_bwd_ref16_rows_h, REF 2 / 3 / 4): dL/dsigma and dL/dcolor arrive as the
+// f16 values the f16 composite backward writes (10 B per row instead of 20) and are
+// converted to f32 as they are loaded; everything after the load is the f32 form's code.
+template <int W, int NHD, bool FAST, bool ROWS, bool BF, int REF = 0, bool HG = false>
 __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64_t tpw,
                                                      const float* wmax) {
   static_assert(!(REF && BF), "reference numerics are f16");
+  static_assert(!HG || REF >= 2, "f16 gradients: the reference-numerics f16-rows forms");
+  using RawRows = RawRowsT<HG>;
   static_assert(REF < 3 || FAST, "the pos / list passes use the fast d_color layout");
   constexpr bool RMASK = REF >= 2;
   constexpr bool POS = REF == 4;  // no dir network in this kernel
@@ -1268,7 +1353,8 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) load_rows<ROWS>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
+      for (int mt = 0; mt < MT; ++mt)
+        load_rows<ROWS, HG>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
     }
     const bool full = FULL;
     {
@@ -1674,13 +1760,14 @@ static BwdGeom bwd_geom(int64_t M, bool fast) {
 
 // the reference-numerics pos pass (REF 4): its own occupancy (no dir network's registers
 // or LDS sums); the list pass (REF 3): one block per CU slot of its occupancy
-template <int W, int NHD>
+template <int W, int NHD, bool HG>
 static BwdGeom pos_geom(int64_t M) {
   const int waves = 4;
   static int p = 0;
   if (p == 0) {
     int nb = 0;
-    const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 4>);
+    const void* fn =
+        reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 4, HG>);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, 0) != hipSuccess || nb < 1) nb = 1;
     p = nb;
   }
@@ -1691,12 +1778,13 @@ static BwdGeom pos_geom(int64_t M) {
   const int64_t nw = blocks * waves;
   return {blocks, nw, (tiles + nw - 1) / nw};
 }
-template <int W, int NHD>
+template <int W, int NHD, bool HG>
 static int64_t list_blocks() {
   static int p = 0;
   if (p == 0) {
     int nb = 0;
-    const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 3>);
+    const void* fn =
+        reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 3, HG>);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) nb = 1;
     p = nb;
   }
@@ -1734,16 +1822,23 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
     if (blocks < 1) blocks = 1;
     // the uniform-tile form (see fwd_kernel): dense rows whose 16-row tiles are one ray each,
     // 4 colour outputs in 16-byte aligned rows, byte offsets of the outputs below 2^31
+    const bool ho = a.color_h != nullptr;  // f16 outputs (same grid as the f32 form)
     const bool ut = g_fwd_ut && a.rows == nullptr && a.n_per_ray % 16 == 0 && a.n_out == 4 &&
-                    (a.color_stride & 3) == 0 && a.M * a.color_stride * 4 < (int64_t{1} << 31);
-#define ANR_FWD_LAUNCH(ROWSV, BSV) \
-  hipLaunchKernelGGL((fwd_kernel<W, NHD, ROWSV, BF, BSV>), dim3(blocks), dim3(64 * waves), 0, st, a)
-    if (a.rows)
-      ANR_FWD_LAUNCH(true, false);
+                    (a.color_stride & 3) == 0 &&
+                    a.M * a.color_stride * (ho ? 2 : 4) < (int64_t{1} << 31);
+#define ANR_FWD_LAUNCH(ROWSV, BSV, HOV)                                                      \
+  hipLaunchKernelGGL((fwd_kernel<W, NHD, ROWSV, BF, BSV, HOV>), dim3(blocks), dim3(64 * waves), \
+                     0, st, a)
+    if (ho) {
+      if (a.rows) return 1;
+      if (ut) ANR_FWD_LAUNCH(false, true, true);
+      else ANR_FWD_LAUNCH(false, false, true);
+    } else if (a.rows)
+      ANR_FWD_LAUNCH(true, false, false);
     else if (ut)
-      ANR_FWD_LAUNCH(false, true);
+      ANR_FWD_LAUNCH(false, true, false);
     else
-      ANR_FWD_LAUNCH(false, false);
+      ANR_FWD_LAUNCH(false, false, false);
 #undef ANR_FWD_LAUNCH
     return 0;
   }
@@ -1755,7 +1850,9 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
     hipLaunchKernelGGL((density_kernel<W, NHD, BF>), dim3(blocks), dim3(64 * waves), 0, st, a);
     return 0;
   }
-  const bool fast = a.n_out == 4 && (a.d_color_stride & 3) == 0 && a.d_sigma != nullptr;
+  const bool hg = a.d_color_h != nullptr;  // f16 gradients (the f16-rows forms only)
+  const bool fast = a.n_out == 4 && (a.d_color_stride & 3) == 0 &&
+                    (hg ? a.d_sigma_h != nullptr : a.d_sigma != nullptr);
   if (a.loss_scale > 0.0f) {  // reference numerics: the register-transposed kernel, REF
     if constexpr (BF) {
       return 1;
@@ -1766,18 +1863,36 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
 #define ANR_REF_BWD(FASTV, REFV)                                                             \
   hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, FASTV, false, false, REFV>), grid, block, 0, st, a, \
                      0.0f, gm.tpw, nullptr)
-      if (a.d_enc_h && fast && a.tile_list) {
+      if (hg) {  // the same three forms (and grids) as the f32-gradient branches below
+        if (!a.d_enc_h) return 1;
+        if (fast && a.tile_list) {
+          const BwdGeom pg = pos_geom<W, NHD, true>(a.M);
+          if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess) return 1;
+          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 4, true>),
+                             dim3(static_cast<unsigned>(pg.blocks)), block, 0, st, a, 0.0f,
+                             pg.tpw, nullptr);
+          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 3, true>),
+                             dim3(static_cast<unsigned>(list_blocks<W, NHD, true>())), block, 0,
+                             st, a, 0.0f, int64_t{0}, nullptr);
+        } else if (fast) {
+          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 2, true>), grid, block, 0,
+                             st, a, 0.0f, gm.tpw, nullptr);
+        } else {
+          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, false, false, false, 2, true>), grid, block,
+                             0, st, a, 0.0f, gm.tpw, nullptr);
+        }
+      } else if (a.d_enc_h && fast && a.tile_list) {
         // the pos pass over every tile (more waves per SIMD: no dir network in it), then the
         // list pass over the tiles it left (nonzero dL/dcolor), at most one per wavefront
         // of a grid of its occupancy
-        const BwdGeom pg = pos_geom<W, NHD>(a.M);
+        const BwdGeom pg = pos_geom<W, NHD, false>(a.M);
         if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess) return 1;
         hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 4>),
                            dim3(static_cast<unsigned>(pg.blocks)), block, 0, st, a, 0.0f, pg.tpw,
                            nullptr);
         hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 3>),
-                           dim3(static_cast<unsigned>(list_blocks<W, NHD>())), block, 0, st, a,
-                           0.0f, int64_t{0}, nullptr);
+                           dim3(static_cast<unsigned>(list_blocks<W, NHD, false>())), block, 0, st,
+                           a, 0.0f, int64_t{0}, nullptr);
       } else if (a.d_enc_h) {
         if (fast) ANR_REF_BWD(true, 2);
         else ANR_REF_BWD(false, 2);
@@ -1998,8 +2113,9 @@ extern "C" int anr_ingp_field_pack(const anr_mlp_desc* pos, const anr_mlp_desc* 
 
 static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t mma_dtype,
                      const void* packed, const void* enc, int64_t enc_stride, const float* dirs,
-                     int64_t n_per_ray, int64_t M, const int32_t* rows, float* sigma,
-                     float* color, int64_t color_stride, anr_stream_t stream) {
+                     int64_t n_per_ray, int64_t M, const int32_t* rows, void* sigma,
+                     void* color, int64_t color_stride, anr_stream_t stream,
+                     bool half_out = false) {
   const int v = variant(pos, dir);
   ANR_CHECK_ARG(v != 0, "anr_ingp_field_fwd: unsupported pos/dir MLP pair");
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_fwd: mma_dtype must be ANR_F16 or ANR_BF16");
@@ -2020,8 +2136,17 @@ static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   a.n_per_ray = static_cast<uint32_t>(n_per_ray);
   a.M = M;
   a.n_out = dir->n_output;
-  a.sigma = sigma;
-  a.color = color;
+  if (half_out) {
+    ANR_CHECK_ARG(rows == nullptr, "anr_ingp_field_fwd_h: dense rows only");
+    // 4-wide colour rows go out as one 8-byte store
+    ANR_CHECK_ARG((color_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(color) & 7) == 0,
+                  "anr_ingp_field_fwd_h: color must be 8-byte aligned");
+    a.sigma_h = static_cast<_Float16*>(sigma);
+    a.color_h = static_cast<_Float16*>(color);
+  } else {
+    a.sigma = static_cast<float*>(sigma);
+    a.color = static_cast<float*>(color);
+  }
   a.color_stride = color_stride;
   a.rows = rows;
   ANR_CHECK_ARG(dispatch(v, mma_dtype == ANR_BF16, 1, a, nullptr, 0,
@@ -2092,12 +2217,13 @@ extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const floa
 
 static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t mma_dtype,
                      const void* packed, const void* enc, int64_t enc_stride, const float* dirs,
-                     int64_t n_per_ray, int64_t M, const int32_t* rows, const float* d_sigma,
-                     const float* d_color, int64_t d_color_stride, float* d_enc,
+                     int64_t n_per_ray, int64_t M, const int32_t* rows, const void* d_sigma,
+                     const void* d_color, int64_t d_color_stride, float* d_enc,
                      int64_t d_enc_stride, float* g_pos, float* g_dir, void* workspace,
                      int64_t workspace_bytes, anr_stream_t stream, float loss_scale = 0.0f,
                      uint8_t* tile_nz = nullptr, void* d_enc_h = nullptr,
-                     uint32_t* row_nz = nullptr, void* tiles_ws = nullptr) {
+                     uint32_t* row_nz = nullptr, void* tiles_ws = nullptr,
+                     bool half_grad = false) {
   const int v = variant(pos, dir);
   ANR_CHECK_ARG(v != 0, "anr_ingp_field_bwd: unsupported pos/dir MLP pair");
   ANR_CHECK_ARG(loss_scale == 0.0f || (loss_scale > 0.0f && mma_dtype == ANR_F16 && rows == nullptr),
@@ -2126,8 +2252,16 @@ static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   a.n_per_ray = static_cast<uint32_t>(n_per_ray);
   a.M = M;
   a.n_out = dir->n_output;
-  a.d_sigma = d_sigma;
-  a.d_color = d_color;
+  if (half_grad) {  // f16 dL/dsigma, dL/dcolor: 4-wide rows are read as one 8-byte load
+    ANR_CHECK_ARG(d_enc_h != nullptr, "anr_ingp_field_bwd: f16 gradients need the f16-rows form");
+    ANR_CHECK_ARG((d_color_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(d_color) & 7) == 0,
+                  "anr_ingp_field_bwd: f16 d_color must be 8-byte aligned");
+    a.d_sigma_h = static_cast<const _Float16*>(d_sigma);
+    a.d_color_h = static_cast<const _Float16*>(d_color);
+  } else {
+    a.d_sigma = static_cast<const float*>(d_sigma);
+    a.d_color = static_cast<const float*>(d_color);
+  }
   a.d_color_stride = d_color_stride;
   a.d_enc = d_enc;
   a.d_enc_stride = d_enc_stride;
@@ -2159,6 +2293,15 @@ extern "C" int anr_ingp_field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* d
                                   anr_stream_t stream) {
   return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
                    sigma, color, color_stride, stream);
+}
+
+extern "C" int anr_ingp_field_fwd_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
+                                    int32_t mma_dtype, const void* packed, const void* enc,
+                                    int64_t enc_stride, const float* dirs, int64_t n_per_ray,
+                                    int64_t M, void* sigma, void* color, int64_t color_stride,
+                                    anr_stream_t stream) {
+  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
+                   sigma, color, color_stride, stream, true);
 }
 
 extern "C" int anr_ingp_field_density(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -2252,6 +2395,29 @@ extern "C" int anr_ingp_field_bwd_ref16_rows(const anr_mlp_desc* pos, const anr_
   return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
                    d_sigma, d_color, d_color_stride, nullptr, d_enc_stride, g_pos, g_dir, nullptr,
                    0, stream, loss_scale, nullptr, d_enc_h, row_nz, workspace);
+}
+
+extern "C" int anr_ingp_field_bwd_ref16_rows_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
+                                               const void* packed, const void* enc,
+                                               int64_t enc_stride, const float* dirs,
+                                               int64_t n_per_ray, int64_t M, const void* d_sigma,
+                                               const void* d_color, int64_t d_color_stride,
+                                               void* d_enc_h, int64_t d_enc_stride, float* g_pos,
+                                               float* g_dir, float loss_scale, uint32_t* row_nz,
+                                               void* workspace, int64_t workspace_bytes,
+                                               anr_stream_t stream) {
+  ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_rows_h: loss_scale must be > 0");
+  ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr,
+                "anr_ingp_field_bwd_ref16_rows_h: null d_enc / row_nz");
+  ANR_CHECK_ARG(workspace == nullptr ||
+                    workspace_bytes >= anr_ingp_field_bwd_ref16_rows_workspace_bytes(M),
+                "anr_ingp_field_bwd_ref16_rows_h: workspace smaller than "
+                "anr_ingp_field_bwd_ref16_rows_workspace_bytes()");
+  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                "anr_ingp_field_bwd_ref16_rows_h: workspace must be 256-byte aligned");
+  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
+                   d_sigma, d_color, d_color_stride, nullptr, d_enc_stride, g_pos, g_dir, nullptr,
+                   0, stream, loss_scale, nullptr, d_enc_h, row_nz, workspace, true);
 }
 
 extern "C" int anr_ingp_field_fwd_rows(const anr_mlp_desc* pos, const anr_mlp_desc* dir,

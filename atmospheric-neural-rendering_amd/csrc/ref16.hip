@@ -21,6 +21,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "anr_common.h"
 
 namespace anr {
@@ -56,6 +58,24 @@ __device__ __forceinline__ float h64(double d) {
 
 template <typename T>
 __device__ __forceinline__ float ld(const T* p, int64_t i) { return to_f32<T>(p[i]); }
+
+// An input as the f16 value the reference holds: f32 storage is rounded as it is read (a
+// tcnn output would have been); f16 storage (the field's f16 outputs, the composite's own
+// f16 copies) holds that value already, and rounding it again is an identity that costs
+// two conversions per value.
+template <typename T>
+__device__ __forceinline__ float in16(float x) {
+  if constexpr (std::is_same<T, __half>::value) return x;
+  else return h(x);
+}
+
+// One sample's 4 colour bands as one 8-byte load (f16 storage, C == 4, 8-byte aligned base)
+typedef _Float16 h4v __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ bool color_vec4(const T* color, int C) {
+  return std::is_same<T, __half>::value && C == 4 &&
+         (reinterpret_cast<uintptr_t>(color) & 7) == 0;
+}
 
 // delta_i = diff([0, (z_0 + z_1) / 2, ..., (z_{N-2} + z_{N-1}) / 2, z_{N-1}])_i in f16
 // (graphics_utils.py:31-35), z_vals (f32) * scale -> f16 first (graphics_utils.py:28); from
@@ -97,9 +117,15 @@ struct SegIn {
         zp[r] = i < N - 1 ? zr[i + 1] : 0.0f;
         if (SIGMA) sg[r] = ld(sigma, b * N + i);
         if (COLOR) {
+          const bool cvec = color_vec4(color, C);
+          h4v v = {0, 0, 0, 0};
+          if (cvec) v = *reinterpret_cast<const h4v*>(color + (b * N + i) * 4);
 #pragma unroll
           for (int c = 0; c < kMaxC; ++c)
-            if (c < C) col[r][c] = ld(color, (b * N + i) * C + c);
+            if (c < C && !cvec) col[r][c] = ld(color, (b * N + i) * C + c);
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (cvec) col[r][c] = static_cast<float>(v[c]);
         }
       }
     }
@@ -194,7 +220,7 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
     for (int r = 0; r < R; ++r) {
       if (r < nr && lane < n) {
         const int64_t b = b0 + r;
-        const float sg = h(cur.sg[r]);
+        const float sg = in16<T>(cur.sg[r]);
         if (sigma16) sigma16[b * N + s0 + lane] = __float2half_rn(sg);
         const Sample sm = sample(sg, delta_z(cur.zm[r], cur.z0[r], cur.zp[r], zs, s0 + lane, N));
         L.q2[r][lane] = static_cast<_Float16>(sm.q2);
@@ -227,7 +253,7 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c) {
           if (c >= C) break;
-          const float col = h(cur.col[r][c]);
+          const float col = in16<T>(cur.col[r][c]);
           if (color16) color16[i * C + c] = __float2half_rn(col);
           L.t[c][r][lane] = static_cast<_Float16>(h(col * w));  // (:48)
         }
@@ -262,7 +288,8 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
 // Autograd of fwd_kernel for dL/dcolor_map (oracle/ref_f16.py render_bwd). d_sigma
 // (one value per sample) doubles as the scratch holding the forward's cumprod outputs T_i,
 // and d_color's first band as the one holding exp(-sigma * delta), both read back in the
-// reverse pass before the gradients overwrite them. Same R-rays-per-wave
+// reverse pass before the gradients overwrite them (f16 outputs: both as one 4-byte pair
+// per sample inside the ray's d_color rows, see `pair` below). Same R-rays-per-wave
 // phases as fwd_kernel: pass 1 replays the cumprod; pass 2 walks the segments from the
 // last, with the reversed cumsum (rc) as the one serial scan.
 template <int R>
@@ -289,6 +316,26 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
   const int nr = B - b0 < R ? static_cast<int>(B - b0) : R;
   const int lane = threadIdx.x;
   const int sr = lane / C, sc = lane - sr * C;
+  // f16 gradient outputs: T_k and exp(-sigma * delta) are parked as ONE aligned 4-byte pair
+  // per sample (T in the low half), sample i of a ray at word i of the ray's own d_color
+  // rows -- contiguous, where the two separate slots are a 2-byte access at a 2 C-byte
+  // pitch (whole lines moved for a quarter of their bytes at C = 4). The ray's 4 N bytes of
+  // pairs fit its 2 C N bytes of d_color from C = 2 up. Pass 2 walks the segments from the
+  // last and writes sample k's gradients at bytes 2 C k and up of the ray, never below
+  // 4 k, so it overwrites only pairs of samples >= k, all read before (the loads precede
+  // the stores in program order, one wavefront). Needs 4-byte aligned rays (N C even);
+  // otherwise, and at C = 1 (a 2-byte pitch already), the two-slot form below runs.
+  // The f32-output instantiations keep the two-slot form as it was.
+  constexpr bool GH = std::is_same<G, __half>::value;
+  typedef uint32_t __attribute__((may_alias)) pair_t;
+  const bool pair = GH && C >= 2 && ((static_cast<int64_t>(N) * C) & 1) == 0 &&
+                    (reinterpret_cast<uintptr_t>(d_color) & 3) == 0;
+  auto park = [&](int64_t b) { return reinterpret_cast<pair_t*>(d_color + b * N * C); };
+  auto in = [](float x) {  // an input as its f16 value
+    if constexpr (GH) return in16<T>(x);
+    else return h(x);
+  };
+  const bool cvec = GH && color_vec4(color, C);
   float gl = 0.0f;  // lane sr < nr: ray sr's band sc
   if (sr < nr) {
     gl = __half2float(g_cm[(b0 + sr) * C + sc]);
@@ -305,17 +352,20 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
     const int nv = (n + 7) & ~7;
     const SegIn<R, false, true> cur = nxt;
     if (s0 + kSeg < N) nxt.fetch(z, sigma, color, b0, nr, s0 + kSeg, N, C, lane);
+    float e1[R];  // pair form: exp(-sigma * delta), stored with T_k after the scan
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       bool zr = false;
+      e1[r] = 0.0f;
       if (r < nr && lane < n) {
         const int64_t b = b0 + r;
-        const Sample sm = sample(h(cur.sg[r]),
+        const Sample sm = sample(in(cur.sg[r]),
                                  delta_z(cur.zm[r], cur.z0[r], cur.zp[r], zs, s0 + lane, N));
         L.q2[r][lane] = static_cast<_Float16>(sm.q2);
         // exp(-sigma * delta) (an f16 value) parked in the sample's first d_color slot until
         // pass 2 reads it back before writing that slot: one f64 exp per sample
-        d_color[(b * N + s0 + lane) * C] = static_cast<G>(sm.e);
+        e1[r] = sm.e;
+        if (!(GH && pair)) d_color[(b * N + s0 + lane) * C] = static_cast<G>(sm.e);
         zr = sm.q2 == 0.0f;
       } else if (lane < nv) {
         L.q2[r][lane] = static_cast<_Float16>(1.0f);
@@ -339,8 +389,15 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
     wave_sync();
 #pragma unroll
     for (int r = 0; r < R; ++r)
-      if (r < nr && lane < n)
-        d_sigma[(b0 + r) * N + s0 + lane] = static_cast<G>(static_cast<float>(L.u[r][lane]));
+      if (r < nr && lane < n) {
+        if (GH && pair) {
+          const uint32_t tb = __builtin_bit_cast(uint16_t, L.u[r][lane]);
+          const uint32_t eb = __builtin_bit_cast(uint16_t, static_cast<_Float16>(e1[r]));
+          park(b0 + r)[s0 + lane] = tb | (eb << 16);
+        } else {
+          d_sigma[(b0 + r) * N + s0 + lane] = static_cast<G>(static_cast<float>(L.u[r][lane]));
+        }
+      }
     wave_sync();
   }
   // surface term: surf = pr * cs -> dL/dpr (sum over bands), dL/dcs
@@ -380,11 +437,31 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
         z0_[r] = zr[i];
         zm_[r] = i > 0 ? zr[i - 1] : 0.0f;
         zp_[r] = i < N - 1 ? zr[i + 1] : 0.0f;
-        ee_[r] = static_cast<float>(d_color[k * C]);
-        tt_[r] = static_cast<float>(d_sigma[k]);
+        if constexpr (GH) {
+          uint32_t pv;
+          if (pair) {
+            pv = park(b0 + r)[i];
+          } else {
+            const uint32_t tb = __builtin_bit_cast(uint16_t, d_sigma[k]);
+            const uint32_t eb = __builtin_bit_cast(uint16_t, d_color[k * C]);
+            pv = tb | (eb << 16);
+          }
+          tt_[r] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(pv)));
+          ee_[r] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(pv >> 16)));
+        } else {
+          ee_[r] = static_cast<float>(d_color[k * C]);
+          tt_[r] = static_cast<float>(d_sigma[k]);
+        }
+        h4v v = {0, 0, 0, 0};
+        if (GH && cvec) v = *reinterpret_cast<const h4v*>(color + k * 4);
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c)
-          if (c < C) col_[r][c] = ld(color, k * C + c);
+          if (c < C && !(GH && cvec)) col_[r][c] = ld(color, k * C + c);
+        if constexpr (GH) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (cvec) col_[r][c] = static_cast<float>(v[c]);
+        }
       }
     }
   };
@@ -423,8 +500,8 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
       for (int c = 0; c < kMaxC; ++c) {
         if (c >= C) break;
         const float gc = L.g[r][c];
-        const float col = h(ccol[r][c]);
-        gw = gw + h(gc * col);                                    // sum_to_size over bands
+        const float col = in(ccol[r][c]);
+        gw = gw + h(gc * col);                                   // sum_to_size over bands
         d_color[k * C + c] = static_cast<G>(h(gc * w));           // color * w -> color
       }
       gw = h(gw);

@@ -29,7 +29,11 @@
 extern "C" {
 #endif
 
-/* ABI 4 (r06): anr_ingp_hash_field_fwd. ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused
+/* ABI 5 (r06): anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and its workspace size;
+ * added since without a version change (additive): anr_ingp_field_fwd_h,
+ * anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16 interchange between the
+ * field and the f16 composite).
+ * ABI 4 (r06): anr_ingp_hash_field_fwd. ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused
  * field entry points' enc_stride < 0
  * selecting the level-quad-plane layout it writes. */
 #define ANR_ABI_VERSION 5
@@ -344,6 +348,14 @@ int anr_ingp_field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t
                        const void* packed, const void* enc, int64_t enc_stride,
                        const float* dirs, int64_t n_per_ray, int64_t M, float* sigma,
                        float* color, int64_t color_stride, anr_stream_t stream);
+/* anr_ingp_field_fwd with f16 outputs: sigma (M) and color (M, color_stride) halves, each
+ * the f32 value anr_ingp_field_fwd stores rounded to nearest even (above 65,504: inf) --
+ * tcnn's f16 module outputs, as the reference-numerics composite reads them. color 8-byte
+ * aligned when color_stride is a multiple of 4. Same kernel forms and grids. */
+int anr_ingp_field_fwd_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t mma_dtype,
+                         const void* packed, const void* enc, int64_t enc_stride,
+                         const float* dirs, int64_t n_per_ray, int64_t M, void* sigma,
+                         void* color, int64_t color_stride, anr_stream_t stream);
 /* Hash-grid forward + field forward in one kernel (ABI 4, r06): the level-quad planes of
  * anr_hashgrid_fwd_planes (written for the backward: planes, plane_stride >= 8 M f16
  * elements) and sigma / color of anr_ingp_field_fwd, bit-identical to those two calls, with
@@ -561,7 +573,9 @@ int anr_composite_ref16_fwd(const float* z, float z_scale, const void* color,
                             void* color_map_atmo, void* color_map_surf, void* weights,
                             void* alpha, void* color16, void* sigma16, anr_stream_t stream);
 /* Backward from dL/dcolor_map (B,C) f16 (torch's f16 autograd of the forward).
- * d_color (B,N,C), d_sigma (B,N,1) [required; also scratch for the cumprod outputs] and
+ * d_color (B,N,C), d_sigma (B,N,1) [required; both also scratch between the kernel's two
+ * passes: the cumprod outputs and exp(-sigma delta), with out_dtype f16 and C >= 2 as one
+ * 4-byte pair per sample in the ray's d_color rows] and
  * d_color_surf (B,C) (nullable) in out_dtype, holding f16 values. zero_rays: one int32
  * (device), incremented per ray in which alpha rounded to exactly 1 (torch's zero-input
  * backward branches, not reproduced: that ray's gradients are 0). */
@@ -623,6 +637,18 @@ int anr_ingp_field_bwd_ref16_rows(const anr_mlp_desc* pos, const anr_mlp_desc* d
                                   float* g_pos, float* g_dir, float loss_scale,
                                   uint32_t* row_nz, void* workspace, int64_t workspace_bytes,
                                   anr_stream_t stream);
+/* anr_ingp_field_bwd_ref16_rows reading d_sigma (M) and d_color (M, d_color_stride) as f16
+ * (the f16 composite backward's outputs; d_color 8-byte aligned when d_color_stride is a
+ * multiple of 4). f16 -> f32 is exact: the same results as the f32 entry on the same
+ * values, from half the gradient bytes. */
+int anr_ingp_field_bwd_ref16_rows_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
+                                    const void* packed, const void* enc, int64_t enc_stride,
+                                    const float* dirs, int64_t n_per_ray, int64_t M,
+                                    const void* d_sigma, const void* d_color,
+                                    int64_t d_color_stride, void* d_enc_h, int64_t d_enc_stride,
+                                    float* g_pos, float* g_dir, float loss_scale,
+                                    uint32_t* row_nz, void* workspace, int64_t workspace_bytes,
+                                    anr_stream_t stream);
 /* anr_mlp_bwd_ws in f16 with tcnn's fixed loss scale: dL/dinput written as
  * f16(f16(g_scaled)/loss_scale). Specialised (fused) MLP shapes only. */
 int anr_mlp_bwd_ref16(const anr_mlp_desc* d, const void* params, const void* in,

@@ -50,16 +50,26 @@ TAGS = {  # prefixes: one instantiation of each per bench run (width / dtype fol
     "hash_bwd": "hashgrid_bwd_v2_kernel<3, __half, 3, 32, false, 6, true>",
     "hash_bwd_build": "hashgrid_bwd_v2_kernel<3, float, 3, 32, false, 6, false>",
     "hash_bwd_rtstride": "hashgrid_bwd_v2_kernel<3, float, 0, 0>",
-    "field_fwd": "field::fwd_kernel<",
-    # reference numerics: the pos pass (zero-colour tiles) and the list pass (r06)
-    "field_bwd": "field::bwd_rt_kernel<64, 2, true, false, false, 4>",
-    "field_bwd_list": "field::bwd_rt_kernel<64, 2, true, false, false, 3>",
-    "field_bwd_build": "field::bwd_rt_kernel<64, 2, true, false, false, 0>",
+    # last argument: f16 outputs (reference numerics; false with ANR_REF_F16_IO=0 and in the
+    # build numerics' leg of the same run). A tuple: every part must occur in the name
+    "field_fwd": ("field::fwd_kernel<", ", true>(anr::field::Args)"),
+    "field_fwd_f32io": ("field::fwd_kernel<", ", false>(anr::field::Args)"),
+    # reference numerics: the pos pass (zero-colour tiles) and the list pass (r06), reading
+    # f16 gradients (last argument true; false with ANR_REF_F16_IO=0: the _f32io tags)
+    "field_bwd": "field::bwd_rt_kernel<64, 2, true, false, false, 4, true>",
+    "field_bwd_list": "field::bwd_rt_kernel<64, 2, true, false, false, 3, true>",
+    "field_bwd_f32io": "field::bwd_rt_kernel<64, 2, true, false, false, 4, false>",
+    "field_bwd_list_f32io": "field::bwd_rt_kernel<64, 2, true, false, false, 3, false>",
+    "field_bwd_build": "field::bwd_rt_kernel<64, 2, true, false, false, 0, false>",
     "field_bwd_lds": "field::bwd_kernel<",
     "composite_fwd": "rb::fwd_kernel<float, 4, 1, 4>",
     "composite_bwd": "rb::bwd_kernel<float, 4, 1, 4>",
     "sampler": "sample_uniform_bins_kernel",
 }
+
+
+def _match(pat, name: str) -> bool:
+    return all(p in name for p in ((pat,) if isinstance(pat, str) else pat))
 
 
 def per_launch(path: str) -> dict[str, float]:
@@ -121,9 +131,9 @@ def main(src: str, tag: str, key_suffix: str = "baseline:8192x1024"):
     apath = os.path.join(src, "atomic", "run_counter_collection.csv")
     atomic = per_launch(apath) if os.path.exists(apath) else {}
     for t, pat in TAGS.items():
-        f = next((v for k, v in fetch.items() if pat in k), None)
-        w = next((v for k, v in write.items() if pat in k), None)
-        a = next((v for k, v in atomic.items() if pat in k), None)
+        f = next((v for k, v in fetch.items() if _match(pat, k)), None)
+        w = next((v for k, v in write.items() if _match(pat, k)), None)
+        a = next((v for k, v in atomic.items() if _match(pat, k)), None)
         if f is not None and w is not None:
             ent = {"bytes": round((2 * f + w) * 1024), "fetch_kib": round(f, 1),
                    "write_kib": round(w, 1), "source": tag}

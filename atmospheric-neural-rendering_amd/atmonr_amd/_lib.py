@@ -134,6 +134,8 @@ _SIGNATURES = {
     "anr_preprocess_points": (c_int32, [_P, c_int64, POINTER(PrepParams), _P, _P]),
     "anr_preprocess_points_f64": (c_int32, [_P, c_int64, POINTER(PrepParams), _P, _P]),
     "anr_preprocess_points_bwd": (c_int32, [_P, c_int64, POINTER(PrepParams), _P, _P, _P]),
+    "anr_append_heights": (c_int32, [_P, c_int64, POINTER(PrepParams), _P, _P]),
+    "anr_append_heights_f64": (c_int32, [_P, c_int64, POINTER(PrepParams), _P, _P]),
     "anr_posenc_width": (c_int32, [POINTER(PosencDesc)]),
     "anr_posenc_fwd": (c_int32, [POINTER(PosencDesc), _P, c_int64, c_int64, _P, c_int64, _P]),
     "anr_posenc_bwd": (c_int32, [POINTER(PosencDesc), _P, c_int64, _P, c_int64, _P, _P]),
@@ -156,6 +158,10 @@ _SIGNATURES = {
          _P],
     ),
     "anr_hashgrid_init": (
+        c_int32,
+        [POINTER(HashGridDesc), c_int32, c_int32, c_int32, c_int32, c_float, c_int32],
+    ),
+    "anr_hashgrid_init_nd": (
         c_int32,
         [POINTER(HashGridDesc), c_int32, c_int32, c_int32, c_int32, c_float, c_int32],
     ),
@@ -575,11 +581,32 @@ def pack_source(param: torch.Tensor, mma_dtype: int) -> torch.Tensor:
 
 
 def hashgrid_desc(n_dims: int, n_levels: int, n_features: int, base_resolution: int,
-                  per_level_scale: float, log2_hashmap_size: int) -> HashGridDesc:
+                  per_level_scale: float, log2_hashmap_size: int,
+                  allow_4d: bool = False) -> HashGridDesc:
+    """anr_hashgrid_init: 2 or 3 dimensions. ``allow_4d`` (anr_hashgrid_init_nd) also admits
+    the 4-D grid of include_height; the default keeps refusing it, as it always has."""
     d = HashGridDesc()
-    call("anr_hashgrid_init", ctypes.byref(d), n_dims, n_levels, n_features,
+    call("anr_hashgrid_init_nd" if allow_4d else "anr_hashgrid_init", ctypes.byref(d), n_dims,
+         n_levels, n_features,
          base_resolution, per_level_scale, log2_hashmap_size)
     return d
+
+
+def height_params(scale: float, offset, ray_origin_height: float, ngp_remap: bool = False,
+                  alt_compress: float = 1.0, append_height: bool = True) -> PrepParams:
+    """anr_prep_params without a point preprocessor (``point_preprocessor: null``): mode 2,
+    rows [x, y, z, h] with the normalised ellipsoidal height of samplers.append_heights, or
+    (``append_height=False``) mode 0, the raw points. ``offset``: three numbers or a tensor."""
+    p = PrepParams()
+    p.mode = 2 if append_height else 0
+    p.ngp_remap = int(ngp_remap)
+    p.scale = float(scale)
+    off = offset.double().cpu().tolist() if hasattr(offset, "cpu") else list(offset)
+    for k in range(3):
+        p.offset[k] = float(off[k])
+    p.ray_origin_height = float(ray_origin_height)
+    p.alt_compress = float(alt_compress)
+    return p
 
 
 def posenc_desc(L, n_dims: int = 3) -> PosencDesc:

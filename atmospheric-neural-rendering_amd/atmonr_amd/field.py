@@ -57,7 +57,8 @@ class IngpFieldFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, coords, dirs, n_per_ray: int, p_hash, p_pos, p_dir, pipe, rows=None,
                 m_dense: int = 0):
-        """coords (M,3) f32 in hash-grid space; dirs (B,3) f32, one per n_per_ray samples.
+        """coords (M,3) f32 in hash-grid space ((M,4) for a 4-D grid, include_height); dirs
+        (B,3) f32, one per n_per_ray samples.
         With ``rows`` (occupancy culling, atmonr_amd.occupancy): coords are the kept
         samples, rows (M,) int32 their indices among the m_dense ray-major samples; sigma
         and color come back dense (m_dense rows), zero at the culled samples."""
@@ -66,6 +67,7 @@ class IngpFieldFn(torch.autograd.Function):
         M = coords.shape[0]
         enc_mod, pos_mod = pipe.pos_encoder, pipe.pos_mlp
         grid = enc_mod.hash_grids[0]
+        nd = grid.desc.n_dims  # coordinates per row: 3, or 4 with include_height
         cdt = pos_mod.dtype
         prec = _lib.F16 if cdt == torch.float16 else _lib.F32
         t_hash = _lib.compute_copy(p_hash, enc_mod.dtype)
@@ -112,12 +114,12 @@ class IngpFieldFn(torch.autograd.Function):
             nq = (grid.desc.n_levels + 3) // 4
             enc = torch.empty(nq, M, 8, device=dev, dtype=torch.float16)
             enc_ld = -8 * M
-            call("anr_hashgrid_fwd_planes", ctypes.byref(grid.desc), ptr(coords), 3, M,
+            call("anr_hashgrid_fwd_planes", ctypes.byref(grid.desc), ptr(coords), nd, M,
                  ptr(t_hash), dtype_code(t_hash.dtype), ptr(enc), 8 * M, s, tag="hash_fwd")
         else:
             enc = torch.empty(M, grid.n_out, device=dev, dtype=enc_mod.dtype)
             enc_ld = enc.stride(0)
-            call("anr_hashgrid_fwd", ctypes.byref(grid.desc), ptr(coords), 3, M, ptr(t_hash),
+            call("anr_hashgrid_fwd", ctypes.byref(grid.desc), ptr(coords), nd, M, ptr(t_hash),
                  dtype_code(t_hash.dtype), ptr(enc), dtype_code(enc.dtype), enc_ld, s,
                  tag="hash_fwd")
         ctx.enc_ld = enc_ld
@@ -173,6 +175,7 @@ class IngpFieldFn(torch.autograd.Function):
         M = coords.shape[0]
         pos_mod, enc_mod = pipe.pos_mlp, pipe.pos_encoder
         grid = enc_mod.hash_grids[0]
+        nd = grid.desc.n_dims
         prec = _lib.F16 if pos_mod.dtype == torch.float16 else _lib.F32
         p_hash, p_pos, p_dir = ctx.params
         g_hash, direct_h = _grad_target(p_hash, dev)
@@ -192,7 +195,7 @@ class IngpFieldFn(torch.autograd.Function):
              dtype_code(enc.dtype), enc.stride(0), M, ptr(d_pos_out), _lib.F32,
              d_pos_out.stride(0), ptr(d_enc), _lib.F32, d_enc.stride(0), ptr(g_pos), s,
              tag="pos_mlp_bwd")
-        call("anr_hashgrid_bwd", ctypes.byref(grid.desc), ptr(coords), 3, M, ptr(d_enc),
+        call("anr_hashgrid_bwd", ctypes.byref(grid.desc), ptr(coords), nd, M, ptr(d_enc),
              _lib.F32, d_enc.stride(0), ptr(g_hash), s, tag="hash_bwd")
         _done(direct_d, p_dir, direct_p, p_pos, direct_h, p_hash)
         return (None, None, None, None if direct_h else g_hash, None if direct_p else g_pos,
@@ -206,6 +209,7 @@ class IngpFieldFn(torch.autograd.Function):
         s = _lib.stream(dev)
         M = coords.shape[0]
         grid = pipe.pos_encoder.hash_grids[0]
+        nd = grid.desc.n_dims
         p_hash, p_pos, p_dir = ctx.params
         g_hash, direct_h = _grad_target(p_hash, dev)
         g_pos, direct_p = _grad_target(p_pos, dev)
@@ -288,15 +292,15 @@ class IngpFieldFn(torch.autograd.Function):
             pipe._last_hash_bwd = (coords, d_enc, g_hash)
             pipe._last_field_grads = (d_sigma, d_color)
         if row_nz is not None:
-            call("anr_hashgrid_bwd_rows", ctypes.byref(grid.desc), ptr(coords), 3, M,
+            call("anr_hashgrid_bwd_rows", ctypes.byref(grid.desc), ptr(coords), nd, M,
                  ptr(d_enc), _lib.F16, d_enc.stride(0), ptr(g_hash), ptr(row_nz), s,
                  tag="hash_bwd")
         elif tiles is not None:
-            call("anr_hashgrid_bwd_tiles", ctypes.byref(grid.desc), ptr(coords), 3, M,
+            call("anr_hashgrid_bwd_tiles", ctypes.byref(grid.desc), ptr(coords), nd, M,
                  ptr(d_enc), _lib.F32, d_enc.stride(0), ptr(g_hash), ptr(tiles), s,
                  tag="hash_bwd")
         else:
-            call("anr_hashgrid_bwd", ctypes.byref(grid.desc), ptr(coords), 3, M, ptr(d_enc),
+            call("anr_hashgrid_bwd", ctypes.byref(grid.desc), ptr(coords), nd, M, ptr(d_enc),
                  _lib.F32, d_enc.stride(0), ptr(g_hash), s, tag="hash_bwd")
         _done(direct_h, p_hash)
         return (None, None, None, None if direct_h else g_hash, None if direct_p else g_pos,
@@ -314,7 +318,7 @@ def _enc_planes(grid, M: int) -> bool:
     samples at 16 levels the row layout (whose walker falls back to 64-bit indexing) runs."""
     d = grid.desc
     nq = (d.n_levels + 3) // 4
-    return (_ENC_PLANES and d.n_features == 2 and d.n_levels <= 16 and d.n_dims == 3
+    return (_ENC_PLANES and d.n_features == 2 and d.n_levels <= 16 and d.n_dims in (3, 4)
             and 16 * nq * (M + 256) < 2 ** 31)
 
 
@@ -355,7 +359,8 @@ def field_fused(pipe) -> bool:
 
 @torch.no_grad()
 def field_density(pipe, pts: torch.Tensor, run_length: int = 0) -> torch.Tensor:
-    """sigma = relu(pos_mlp(pos_encoder(pts))[:, 0]) at hash-grid points (P, 3) through the
+    """sigma = relu(pos_mlp(pos_encoder(pts))[:, 0]) at hash-grid points (P, 3) ((P, 4) for a
+    4-D grid: anr_append_heights rows) through the
     fused kernels (hash forward, then anr_ingp_field_density: the pos MLP of
     anr_ingp_field_fwd without the dir MLP, bit-identical sigma). The extract path of
     instant_ngp.py:208-247 and the occupancy grid's density function, for pipelines whose
@@ -373,7 +378,8 @@ def field_density(pipe, pts: torch.Tensor, run_length: int = 0) -> torch.Tensor:
     pts = pts.float().contiguous()
     t_hash = _lib.compute_copy(enc_mod.params, enc_mod.dtype)
     enc = torch.empty(P, grid.n_out, device=dev, dtype=torch.float16)
-    call("anr_hashgrid_fwd_runs", ctypes.byref(grid.desc), ptr(pts), 3, P, int(run_length),
+    call("anr_hashgrid_fwd_runs", ctypes.byref(grid.desc), ptr(pts), grid.desc.n_dims, P,
+         int(run_length),
          ptr(t_hash), dtype_code(t_hash.dtype), ptr(enc), _lib.F16, enc.stride(0), s,
          tag="hash_fwd")
     mma = _mma_code(pipe)

@@ -24,6 +24,12 @@ Two numerics (``numerics=`` or the config key ``"numerics"``):
   module backward with f16 gradients at the module boundaries, and tcnn's f16 parameter
   gradients (tinycudann/modules.py). Opt-in, for PSNR parity with the reference; f16
   networks, fused field, no occupancy culling.
+
+``include_height: true`` (needs ``point_preprocessor: null``, as the base class asserts):
+the position grid is 4-D and every sample's normalised ellipsoidal height is its fourth
+coordinate (instant_ngp.py:50,153,227); the results gain ``norm_heights_fine``. The fused
+path computes the height inside the sampler kernel, the unfused path and ``extract`` with
+anr_append_heights. Build numerics only, no occupancy grid (its cells are 3-D).
 """
 
 from __future__ import annotations
@@ -42,7 +48,8 @@ from ..graphics_utils import render_with_surface, render_with_surface_ref16
 from ..losses import LOSSES, indexed_loss, indexed_loss_ref16
 from ..occupancy import OccupancyGrid, pipeline_density
 from ..optim import FusedAdam
-from ..samplers import preprocess_points, sample_and_preprocess, sample_uniform_bins
+from ..samplers import (points_with_heights, preprocess_points, sample_and_preprocess,
+                        sample_uniform_bins)
 from ..tcnn import Encoding, Network
 from .pipeline import Pipeline
 
@@ -67,8 +74,14 @@ class InstantNGPPipeline(Pipeline):
         self.num_density_outputs = 1
         if self.config["multi_band_extinction"]:
             self.num_density_outputs = self.config["num_bands"]
-        if self.config["include_height"]:
-            raise NotImplementedError("include_height is disabled in both reference configs")
+        self.include_height = bool(self.config["include_height"])
+        if self.include_height and numerics == "reference":
+            raise ValueError("include_height runs build numerics only: numerics='reference' "
+                             "(the row-mask hash-grid backward is 3-D) is not supported with it")
+        if self.include_height and (occupancy is not None or
+                                    (self.config.get("occupancy_grid") and numerics == "build")):
+            raise ValueError("include_height does not combine with the occupancy grid "
+                             "(its cells are 3-D)")
         if fused and self.num_density_outputs != 1:
             fused = False
         self.fused = fused
@@ -95,7 +108,8 @@ class InstantNGPPipeline(Pipeline):
         # outputs in reference numerics: the per-ray surface modules here, and the fused
         # field's sigma / colour and their gradients (field.py, ANR_REF_F16_IO)
         fdt = torch.float32 if fused and numerics == "build" else None
-        self.pos_encoder = Encoding(3, ingp["encoding"], seed=seed, dtype=dtype)
+        self.pos_encoder = Encoding(4 if self.include_height else 3, ingp["encoding"], seed=seed,
+                                    dtype=dtype)
         self.pos_mlp = Network(self.pos_encoder.n_output_dims, 16, ingp["network"],
                                seed=seed + 1, dtype=mlp_dtype)
         self.dir_encoder = Encoding(3 + 16 - self.num_density_outputs, ingp["dir_encoding"],
@@ -118,6 +132,15 @@ class InstantNGPPipeline(Pipeline):
         if self.point_preprocessor is not None:
             self._prep_ngp = self.point_preprocessor.params(ngp_remap=True,
                                                             alt_compress=self.alt_compress)
+        else:
+            # point_preprocessor: null -- the raw points (mode 0) or, with include_height,
+            # the raw points plus their height (mode 2), remapped and compressed
+            self._prep_ngp = _lib.height_params(self.scale, self.offset, self.ray_origin_height,
+                                                ngp_remap=True, alt_compress=self.alt_compress,
+                                                append_height=self.include_height)
+        if self.include_height:  # samplers.append_heights' parameters, built once
+            self._prep_height = _lib.height_params(self.scale, self.offset,
+                                                   self.ray_origin_height)
         # occupancy-grid culling (beyond the reference, atmonr_amd.occupancy): off unless
         # passed in or configured; the uniform sampler stays the parity default
         occ_cfg = self.config.get("occupancy_grid")
@@ -228,12 +251,12 @@ class InstantNGPPipeline(Pipeline):
         if occ is not None and occ.active:
             # only samples in occupied cells reach the hash grid and the MLPs; sigma and
             # color come back dense (B*N rows) with zeros at the culled samples
-            rows, kept = occ.compact(coords.view(B * N, 3))
+            rows, kept = occ.compact(coords.view(B * N, 3))  # never with include_height
             sigma, color = IngpFieldFn.apply(kept, ray_batch["dir"].float(), N, *params, rows,
                                              B * N)
         else:
-            sigma, color = IngpFieldFn.apply(coords.view(B * N, 3), ray_batch["dir"].float(), N,
-                                             *params)
+            sigma, color = IngpFieldFn.apply(coords.view(B * N, coords.shape[-1]),
+                                             ray_batch["dir"].float(), N, *params)
         color = color.view(B, N, -1)
         sigma = sigma.view(B, N, 1)
         color_surf = surf_branch()
@@ -250,7 +273,7 @@ class InstantNGPPipeline(Pipeline):
         else:
             color_map, _, weights, atmo, surf = render_with_surface(
                 z_vals, color, sigma, color_surf, z_scale=self.scale / 1000)
-        return {
+        results = {
             "color_fine": color[:, :-1],
             "color_surf": color_surf,
             "color_map_surf": surf,
@@ -260,6 +283,9 @@ class InstantNGPPipeline(Pipeline):
             "weights_fine": weights,
             "z_vals_fine": z_vals,
         }
+        if self.include_height:
+            results["norm_heights_fine"] = coords[..., 3]
+        return results
 
     def _forward_reference(self, ray_batch, u=None):
         # instant_ngp.py:137-206, op for op
@@ -269,6 +295,8 @@ class InstantNGPPipeline(Pipeline):
         if self.point_preprocessor:
             pts = self.point_preprocessor(pts)
         pts = (pts + 1) / 2
+        if self.include_height:  # append_heights(pts, ray_origin_height, scale, offset)
+            pts = points_with_heights(pts, self._prep_height)
         dirs = ray_batch["dir"][:, None].repeat(1, N, 1)
         pts[..., 2] = pts[..., 2] / self.config["alt_compress_factor"]
         pos_enc = self.pos_encoder(pts.view(B_ * N, -1))
@@ -282,7 +310,7 @@ class InstantNGPPipeline(Pipeline):
         sigma = F.relu(sigma)
         color_map, _, weights, atmo, surf = render_with_surface(
             z_vals * (self.scale / 1000), color, sigma, color_surf)
-        return {
+        results = {
             "color_fine": color[:, :-1],
             "color_surf": color_surf,
             "color_map_surf": surf,
@@ -292,6 +320,9 @@ class InstantNGPPipeline(Pipeline):
             "weights_fine": weights,
             "z_vals_fine": z_vals,
         }
+        if self.include_height:
+            results["norm_heights_fine"] = pts[..., 3]
+        return results
 
     @property
     def zero_rays_total(self) -> int:
@@ -308,6 +339,10 @@ class InstantNGPPipeline(Pipeline):
         that does not change the values."""
         if self.point_preprocessor:
             pts = preprocess_points(pts, self._prep_ngp)
+        elif self.include_height:
+            # remap, height and compression in one kernel, in the points' own precision (the
+            # extract script feeds f64), rounded to f32 once as tcnn rounds its input
+            pts = points_with_heights(pts, self._prep_ngp)
         else:
             pts = (pts + 1) / 2
             pts[..., 2] = pts[..., 2] / self.alt_compress

@@ -36,7 +36,10 @@ class NeRFPipeline(Pipeline):
     def __init__(self, config: dict, dataset: Any) -> None:
         super().__init__(config, dataset)
         if config["include_height"]:
-            raise NotImplementedError("include_height is disabled in both reference configs")
+            raise NotImplementedError(
+                "include_height is not supported by the NeRF pipeline: the height of the pdf "
+                "samples needs a backward into the sample positions (the Instant-NGP pipeline "
+                "supports the option)")
         self.nerf = {}
         self.nerf["coarse"], self.nerf["fine"] = get_model(
             hidden_dim=config["mlp_hidden_dim"], N_lambda=config["num_bands"],

@@ -73,7 +73,9 @@ def sample_and_preprocess(
 ) -> tuple[torch.Tensor | None, torch.Tensor, torch.Tensor]:
     """Fused K1+K2: samples, z and the preprocessed (+remapped) hash-grid coordinates.
 
-    Returns (pts or None, z (B, n_bins), coords (B, n_bins, 3)).
+    Returns (pts or None, z (B, n_bins), coords (B, n_bins, 3)). With a ``prep`` of mode 2
+    (:func:`atmonr_amd._lib.height_params`, ``include_height``) coords are (B, n_bins, 4):
+    each sample's normalised ellipsoidal height is appended in the same pass.
     """
     origin, direction, length = ray_batch["origin"], ray_batch["dir"], ray_batch["len"]
     B = origin.shape[0]
@@ -87,11 +89,43 @@ def sample_and_preprocess(
     length = length.float().contiguous()
     pts = torch.empty(B, n_bins, 3, device=device) if want_pts else None
     z = torch.empty(B, n_bins, device=device)
-    coords = torch.empty(B, n_bins, 3, device=device)
+    coords = torch.empty(B, n_bins, 4 if prep.mode == 2 else 3, device=device)
     call("anr_sample_uniform_bins", ptr(origin), ptr(direction), ptr(length),
          ptr(u), ptr(_bins(n_bins, device)), B, n_bins,
          ptr(pts), ptr(z), prep, ptr(coords), _lib.stream(device))
     return pts, z, coords
+
+
+def points_with_heights(pts: torch.Tensor, prep: "_lib.PrepParams") -> torch.Tensor:
+    """(..., 3) f32 or f64 points -> (..., 4) f32 rows [x, y, z, h] (anr_append_heights):
+    with ``prep.ngp_remap`` the Instant-NGP remap, the height of the remapped points and the
+    altitude compression of column 2 (instant_ngp.py:149-160); without it the points as
+    given plus their height. f64 points (the extract path) keep the remap and the compression
+    in f64 and are rounded to f32 once, where tcnn casts the encoder input. No gradient."""
+    if prep.mode != 2:
+        raise _lib.ANRError("points_with_heights needs a PrepParams of mode 2 (_lib.height_params)")
+    shp = pts.shape
+    f64 = pts.dtype == torch.float64
+    flat = pts.detach().reshape(-1, 3)
+    flat = (flat if f64 else flat.float()).contiguous()
+    out = torch.empty(flat.shape[0], 4, device=flat.device, dtype=torch.float32)
+    call("anr_append_heights_f64" if f64 else "anr_append_heights", ptr(flat), flat.shape[0],
+         prep, ptr(out), _lib.stream(flat.device))
+    return out.view(*shp[:-1], 4)
+
+
+def append_heights(pts: torch.Tensor, ray_origin_height: float, scale: float,
+                   offset: torch.Tensor) -> torch.Tensor:
+    """samplers.py:168-195: (B, N, 3) points -> (B, N, 4) with the ellipsoidal height of
+    ``pts * scale + offset`` (f64), divided by ``ray_origin_height`` and rounded to f32,
+    appended. The points are un-normalised as they are given -- the pipeline passes the
+    already remapped ones -- so the height is not confined to [0, 1]. f64 points come back
+    f64 (torch.cat's promotion in the reference); no gradient."""
+    prep = _lib.height_params(scale, offset, ray_origin_height)
+    out = points_with_heights(pts, prep)
+    if pts.dtype == torch.float64:
+        return torch.cat([pts, out[..., 3:].double()], dim=-1)
+    return out
 
 
 class _PreprocessFn(torch.autograd.Function):

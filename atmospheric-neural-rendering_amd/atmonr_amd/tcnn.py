@@ -51,8 +51,8 @@ class _Sub:
 
 class _HashGrid(_Sub):
     def __init__(self, n_in: int, cfg: dict):
-        if n_in not in (2, 3):
-            raise ANRError(f"HashGrid supports 2 or 3 input dims, got {n_in}")
+        if n_in not in (2, 3, 4):
+            raise ANRError(f"HashGrid supports 2, 3 or 4 input dims, got {n_in}")
         self.n_in = n_in
         self.n_levels = int(cfg.get("n_levels", 16))
         self.n_features = int(cfg.get("n_features_per_level", 2))
@@ -63,7 +63,7 @@ class _HashGrid(_Sub):
         if str(interp).lower() != "linear":
             raise ANRError(f"HashGrid interpolation {interp!r} not supported (Linear only)")
         self.desc = _lib.hashgrid_desc(n_in, self.n_levels, self.n_features, self.base_res,
-                                       self.pls, self.log2_T)
+                                       self.pls, self.log2_T, allow_4d=True)
         self.n_out = self.n_levels * self.n_features
         self.n_params = int(self.desc.n_params)
 

@@ -24,6 +24,14 @@ struct GridLevels {
   float scale[ANR_MAX_LEVELS];
 };
 
+// tcnn's coherent-prime table, written out to its seven entries (D <= 4 is compiled)
+__device__ constexpr uint32_t kHashPrimes[7] = {1u,          2654435761u, 805459861u, 3674653429u,
+                                                2097192037u, 1434869437u, 2165219737u};
+
+// The stride loop is tcnn's, in uint32: it stops at the first stride above T, so the largest
+// product formed is (a stride <= T) * res <= T * res. It decides "hashed" exactly as
+// LevelIdx::init (uint64 strides over all D dimensions) while T * res < 2^32: T <= 2^19 up
+// to res = 8191, T <= 2^24 up to res = 255 (config-3 grid, 4-D: T * res <= 2^19 * 2049).
 template <int D>
 __device__ __forceinline__ uint32_t grid_index(uint32_t T, uint32_t res, const uint32_t* g) {
   uint32_t stride = 1, index = 0;
@@ -33,10 +41,9 @@ __device__ __forceinline__ uint32_t grid_index(uint32_t T, uint32_t res, const u
     stride *= res;
   }
   if (T < stride) {
-    constexpr uint32_t primes[3] = {1u, 2654435761u, 805459861u};
     index = 0;
 #pragma unroll
-    for (int d = 0; d < D; ++d) index ^= g[d] * primes[d];
+    for (int d = 0; d < D; ++d) index ^= g[d] * kHashPrimes[d];
     // hashed levels have T = 2^log2_hashmap_size (checked by make_levels): % T == & (T-1)
     return index & (T - 1u);
   }
@@ -55,9 +62,10 @@ struct LevelIdx {
   uint32_t T, mul[D], res1;  // res1 = res - 1
   bool hashed;
   __device__ void init(uint32_t T_, uint32_t res) {
-    constexpr uint32_t primes[3] = {1u, 2654435761u, 805459861u};
     T = T_;
     res1 = res - 1u;
+    // res^D fits uint64 for D <= 4 (res < 2^16); the strides are only used on dense levels,
+    // where every one of them is <= T
     uint64_t st = 1;
     uint32_t stride[D];
 #pragma unroll
@@ -65,9 +73,9 @@ struct LevelIdx {
       stride[d] = static_cast<uint32_t>(st);
       st *= res;
     }
-    hashed = st > T;  // res^D > T, as grid_index decides
+    hashed = st > T;  // res^D > T, as grid_index decides (see there for the range)
 #pragma unroll
-    for (int d = 0; d < D; ++d) mul[d] = hashed ? primes[d] : stride[d];
+    for (int d = 0; d < D; ++d) mul[d] = hashed ? kHashPrimes[d] : stride[d];
   }
   // comp[d][o] = (cell[d] + o) * mul[d]  (uint32 wrap, as tcnn)
   __device__ void dims(const uint32_t* cell, uint32_t (*comp)[2]) const {

@@ -582,7 +582,11 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_planes_kernel(
   const __amdgpu_buffer_rsrc_t ro = wave_rsrc(out, out_bytes);
   const uint32_t xo = static_cast<uint32_t>(m) * xs4;  // past the end: loads return 0
   float xv[D];
-  if constexpr (D == 3) {
+  if constexpr (D == 4) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rx, xo, 0, 0);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) xv[d] = __uint_as_float(v[d]);
+  } else if constexpr (D == 3) {
     const auto v = __builtin_amdgcn_raw_buffer_load_b96(rx, xo, 0, 0);
     xv[0] = __uint_as_float(v[0]);
     xv[1] = __uint_as_float(v[1]);
@@ -1010,7 +1014,9 @@ static int launch_fwd(const GridLevels& G, const anr_hashgrid_desc* d, const flo
                       int64_t x_stride, int64_t M, const void* table, int32_t tdt,
                       void* out, int32_t odt, int64_t out_stride, hipStream_t s,
                       int64_t run = 0) {
-  if (F == 2 && d->n_levels <= 16 && fwd_v6()) {
+  // 4-D runs the generic v1 walker (the v6 walker is specialised for 2 and 3 dimensions)
+  if constexpr (F == 2 && D <= 3)
+  if (d->n_levels <= 16 && fwd_v6()) {
     // 32-bit buffer offsets: every byte range must stay below 2^31
     const int64_t esz_t = tdt == ANR_F16 ? 2 : 4, esz_o = odt == ANR_F16 ? 2 : 4;
     const int64_t x_bytes = ((M - 1) * x_stride + D) * 4;
@@ -1080,7 +1086,9 @@ static int launch_bwd(const GridLevels& G, const anr_hashgrid_desc* d, const flo
   // drop offset at 2 GB): larger tables (2^24 entries x 16 levels) take the v1 walker
   const uint64_t grad_bytes =
       (static_cast<uint64_t>(G.offset[d->n_levels - 1]) + G.size[d->n_levels - 1]) * F * 4u;
-  if (F == 2 && d->n_levels <= 16 && grad_bytes < 0x80000000ull && bwd_v2()) {
+  // 4-D runs the generic v1 walker (LaneCorners, the v2 walker's corner carry, is 2-D / 3-D)
+  if constexpr (F == 2 && D <= 3)
+  if (d->n_levels <= 16 && grad_bytes < 0x80000000ull && bwd_v2()) {
     const int64_t K = pick_chunk_v2(M);
     const int64_t waves = ceil_div(M, K);
     const dim3 grid(static_cast<unsigned>(ceil_div(waves, 4))), block(256);
@@ -1128,12 +1136,14 @@ extern "C" int anr_hashgrid_force_v1(int32_t mode) {
   return prev;
 }
 
-extern "C" int anr_hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t n_levels,
-                                 int32_t n_features, int32_t base_resolution,
-                                 float per_level_scale, int32_t log2_hashmap_size) {
+// max_dims: 3 for anr_hashgrid_init (its contract since ABI 1), 4 for anr_hashgrid_init_nd
+static int hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t max_dims,
+                         int32_t n_levels, int32_t n_features, int32_t base_resolution,
+                         float per_level_scale, int32_t log2_hashmap_size) {
   using namespace anr;
   ANR_CHECK_ARG(d, "anr_hashgrid_init: null desc");
-  ANR_CHECK_ARG(n_dims == 2 || n_dims == 3, "anr_hashgrid_init: n_dims must be 2 or 3");
+  ANR_CHECK_ARG(n_dims >= 2 && n_dims <= max_dims,
+                "anr_hashgrid_init: n_dims must be in [2, %d]", max_dims);
   ANR_CHECK_ARG(n_levels >= 1 && n_levels <= ANR_MAX_LEVELS,
                 "anr_hashgrid_init: n_levels must be in [1, %d]", ANR_MAX_LEVELS);
   ANR_CHECK_ARG(n_features == 1 || n_features == 2 || n_features == 4 || n_features == 8,
@@ -1179,6 +1189,20 @@ extern "C" int anr_hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t n
   return ANR_OK;
 }
 
+extern "C" int anr_hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t n_levels,
+                                 int32_t n_features, int32_t base_resolution,
+                                 float per_level_scale, int32_t log2_hashmap_size) {
+  return hashgrid_init(d, n_dims, 3, n_levels, n_features, base_resolution, per_level_scale,
+                       log2_hashmap_size);
+}
+
+extern "C" int anr_hashgrid_init_nd(anr_hashgrid_desc* d, int32_t n_dims, int32_t n_levels,
+                                    int32_t n_features, int32_t base_resolution,
+                                    float per_level_scale, int32_t log2_hashmap_size) {
+  return hashgrid_init(d, n_dims, 4, n_levels, n_features, base_resolution, per_level_scale,
+                       log2_hashmap_size);
+}
+
 #define ANR_HG_DISPATCH(FN, ...)                                                   \
   switch (d->n_dims * 16 + d->n_features) {                                        \
     case 2 * 16 + 1: return FN<2, 1>(__VA_ARGS__);                                 \
@@ -1189,6 +1213,10 @@ extern "C" int anr_hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t n
     case 3 * 16 + 2: return FN<3, 2>(__VA_ARGS__);                                 \
     case 3 * 16 + 4: return FN<3, 4>(__VA_ARGS__);                                 \
     case 3 * 16 + 8: return FN<3, 8>(__VA_ARGS__);                                 \
+    case 4 * 16 + 1: return FN<4, 1>(__VA_ARGS__);                                 \
+    case 4 * 16 + 2: return FN<4, 2>(__VA_ARGS__);                                 \
+    case 4 * 16 + 4: return FN<4, 4>(__VA_ARGS__);                                 \
+    case 4 * 16 + 8: return FN<4, 8>(__VA_ARGS__);                                 \
     default:                                                                       \
       ::anr::set_error("hashgrid: unsupported n_dims=%d n_features=%d", d->n_dims, \
                        d->n_features);                                             \
@@ -1286,8 +1314,8 @@ extern "C" int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* 
                 "anr_hashgrid_fwd_planes: out and plane_stride must be 16-byte aligned");
   ANR_CHECK_ARG(table_dtype == ANR_F16 || table_dtype == ANR_F32,
                 "anr_hashgrid_fwd_planes: bad dtype");
-  ANR_CHECK_ARG(d->n_features == 2 && d->n_levels <= 16 && (d->n_dims == 2 || d->n_dims == 3),
-                "anr_hashgrid_fwd_planes: 2 features, <= 16 levels, 2-D or 3-D");
+  ANR_CHECK_ARG(d->n_features == 2 && d->n_levels <= 16 && d->n_dims >= 2 && d->n_dims <= 4,
+                "anr_hashgrid_fwd_planes: 2 features, <= 16 levels, 2-D to 4-D");
   GridLevels G;
   ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_fwd_planes: descriptor not initialised");
   const int64_t esz_t = table_dtype == ANR_F16 ? 2 : 4;
@@ -1318,7 +1346,10 @@ extern "C" int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* 
                      static_cast<uint32_t>(x_stride * 4), M, static_cast<const TT*>(table),  \
                      static_cast<uint32_t>(t_bytes), static_cast<__half*>(out),              \
                      static_cast<uint32_t>(o_bytes), static_cast<uint32_t>(plane_stride * 2))
-  if (d->n_dims == 3) {
+  if (d->n_dims == 4) {
+    if (table_dtype == ANR_F16) ANR_HG_PL(4, __half);
+    else ANR_HG_PL(4, float);
+  } else if (d->n_dims == 3) {
     if (table_dtype == ANR_F16) ANR_HG_PL(3, __half);
     else ANR_HG_PL(3, float);
   } else {

@@ -43,6 +43,39 @@ __device__ __forceinline__ double py_mod(double a, double b) {
 }
 
 
+// cartesian_to_horizontal, wgs_84.py:83-97, of one WGS-84 Cartesian point (radians, metres).
+// The sines and cosines of the angles the reference builds with atan2 are formed from the
+// atan2 arguments instead (sin(atan2(p, q)) = p / hypot, cos = q / hypot; cos(lon) = x / D),
+// and every f64 division but five is a multiplication by a reciprocal formed once (alt = x /
+// (cos lat cos lon) = D rl / X): each value moves by an f64 ulp or two, 2^-29 of the f32
+// rounding of the outputs, at about half of the f64 instructions (the kernels that call this
+// are f64-issue-bound). Only lon and lat themselves need atan2; a caller that reads alt only
+// (height_point) pays for neither.
+struct Geodetic {
+  double lat, lon, alt;
+};
+__device__ __forceinline__ Geodetic bowring(double x, double y, double z) {
+  const double lon = atan2(y, x);
+  const double D = sqrt(x * x + y * y);
+  const double iD = 1.0 / D;
+  const double t = z * iD, k = kA / kB;
+  const double ru = sqrt(t * t + k * k);
+  const double iru = 1.0 / ru;
+  const double su = t * iru, cu = k * iru;
+  const double Y = z + (kE2 * kB) * (su * su * su);
+  const double X = D - (kE * kA) * (cu * cu * cu);
+  const double lat = atan2(Y, X);
+  const double rl = sqrt(X * X + Y * Y);
+  const double sl = Y / rl;
+  const double Nr = kA / sqrt(1.0 - kE * (sl * sl));
+  // x / (cos(lat) cos(lon)) (wgs_84.py:96) with cos(lon) = x / D and cos(lat) = X / rl.
+  // Deliberate deviation at x = 0 (lon = +-90 deg): the reference divides 0 by cos(lon)
+  // ~ 6e-17 (a finite value that depends on atan2's last ulp, or inf / NaN), this form
+  // stays finite; no HARP2 scene here reaches it (scenes centred on lon = +-90 deg would)
+  const double alt = (D * rl) / X - Nr;
+  return Geodetic{lat, lon, alt};
+}
+
 // preprocess_coords for one point p (normalized scene frame) -> coords (f32).
 // T = float: the training path (f32 points; the result is cast to f32 before the clip and
 // the NGP remap, harp2.py:384-385). T = double: the extract path (extract.py:206 feeds
@@ -66,35 +99,13 @@ __device__ __forceinline__ void preprocess_point(const PrepDev& P, T px, T py, T
       y = py * P.scale_d + P.offset[1];
       z = pz * P.scale_d + P.offset[2];
     }
-    // cartesian_to_horizontal, wgs_84.py:83-97. The sines and cosines of the angles the
-    // reference builds with atan2 are formed from the atan2 arguments instead
-    // (sin(atan2(p, q)) = p / hypot, cos = q / hypot; cos(lon) = x / D), and every f64
-    // division but five is a multiplication by a reciprocal formed once (alt = x / (cos lat
-    // cos lon) = D rl / X; the degree and range scalings multiply by host-computed
-    // constants): each value moves by an f64 ulp or two, 2^-29 of the f32 rounding of the
-    // outputs, at about half of the f64 instructions (this kernel is f64-issue-bound).
-    // Only lon and lat themselves need atan2.
-    const double lon = atan2(y, x);
-    const double D = sqrt(x * x + y * y);
-    const double iD = 1.0 / D;
-    const double t = z * iD, k = kA / kB;
-    const double ru = sqrt(t * t + k * k);
-    const double iru = 1.0 / ru;
-    const double su = t * iru, cu = k * iru;
-    const double Y = z + (kE2 * kB) * (su * su * su);
-    const double X = D - (kE * kA) * (cu * cu * cu);
-    const double lat = atan2(Y, X);
-    const double rl = sqrt(X * X + Y * Y);
-    const double sl = Y / rl;
-    const double Nr = kA / sqrt(1.0 - kE * (sl * sl));
-    // x / (cos(lat) cos(lon)) (wgs_84.py:96) with cos(lon) = x / D and cos(lat) = X / rl.
-    // Deliberate deviation at x = 0 (lon = +-90 deg): the reference divides 0 by cos(lon)
-    // ~ 6e-17 (a finite value that depends on atan2's last ulp, or inf / NaN), this form
-    // stays finite; no HARP2 scene here reaches it (scenes centred on lon = +-90 deg would)
-    const double alt = (D * rl) / X - Nr;
+    // cartesian_to_horizontal (bowring above); the degree and range scalings multiply by
+    // host-computed constants
+    const Geodetic geo = bowring(x, y, z);
+    const double alt = geo.alt;
     constexpr double kDeg = 180.0 / kPi;
-    double lat_d = lat * kDeg;
-    double lon_d = lon * kDeg;
+    double lat_d = geo.lat * kDeg;
+    double lon_d = geo.lon * kDeg;
     if (P.shift_lon) lon_d = py_mod(lon_d, 360.0) - 180.0;  // harp2.py:379-380
     // harp2.py:381-383
     const double a = (lat_d - P.lat_min) * P.k_lat - 1.0;
@@ -120,6 +131,33 @@ __device__ __forceinline__ void preprocess_point(const PrepDev& P, T px, T py, T
   out[0] = static_cast<float>(cx);
   out[1] = static_cast<float>(cy);
   out[2] = static_cast<float>(cz);
+}
+
+// Mode 2, the Instant-NGP include_height input (instant_ngp.py:149-160, samplers.py:168-195)
+// of one point: the optional (p + 1) / 2 remap in T, then the height appended by
+// append_heights -- which "un-normalises" the points it is given, here the already remapped
+// ones, as p.double() * scale + offset (the multiply in f64, unlike harp2.py:376) and divides
+// the Bowring altitude by ray_origin_height before the one rounding to f32 -- then the
+// altitude compression of column 2 alone. The height comes from the uncompressed column 2
+// and is not confined to [0, 1]. T = double (extract): remap and compression stay in f64
+// and each column is rounded to f32 once, where tcnn casts the encoder input.
+template <typename T>
+__device__ __forceinline__ void height_point(const PrepDev& P, T px, T py, T pz, float* out) {
+  T cx = px, cy = py, cz = pz;
+  if (P.ngp_remap) {
+    cx = (cx + T(1)) / T(2);
+    cy = (cy + T(1)) / T(2);
+    cz = (cz + T(1)) / T(2);
+  }
+  const double x = static_cast<double>(cx) * P.scale_d + P.offset[0];
+  const double y = static_cast<double>(cy) * P.scale_d + P.offset[1];
+  const double z = static_cast<double>(cz) * P.scale_d + P.offset[2];
+  const float h = static_cast<float>(bowring(x, y, z).alt / P.h);
+  if (P.ngp_remap) cz = cz / static_cast<T>(P.alt_compress);
+  out[0] = static_cast<float>(cx);
+  out[1] = static_cast<float>(cy);
+  out[2] = static_cast<float>(cz);
+  out[3] = h;
 }
 
 // ---- backward of preprocess_point (NeRF back-propagates into the sample points through
@@ -216,11 +254,15 @@ __global__ void __launch_bounds__(256) preprocess_points_bwd_kernel(
     dpts[idx * 3 + k] = static_cast<float>(g[0] * J[0][k] + g[1] * J[1][k] + g[2] * J[2][k]);
 }
 
-__global__ void __launch_bounds__(256) sample_uniform_bins_kernel(
+// One sample of the sampler kernels below. kHeight: prep mode 2, coords rows are the 4-wide
+// [x, y, z, h] of height_point (its own kernel, so that the kernel every other mode launches
+// keeps its code and its name)
+template <bool kHeight>
+__device__ __forceinline__ void sample_uniform_bins_body(
     const float* __restrict__ origin, const float* __restrict__ dir,
     const float* __restrict__ len, const float* __restrict__ u,
     const float* __restrict__ bins, int64_t B, int32_t N, float* __restrict__ pts,
-    float* __restrict__ zout, PrepDev P, int do_prep, float* __restrict__ coords) {
+    float* __restrict__ zout, const PrepDev& P, int do_prep, float* __restrict__ coords) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (idx >= B * N) return;
   const int64_t b = idx / N;
@@ -238,13 +280,43 @@ __global__ void __launch_bounds__(256) sample_uniform_bins_kernel(
     pts[idx * 3 + 1] = py;
     pts[idx * 3 + 2] = pz;
   }
-  if (do_prep) {
+  if constexpr (kHeight) {
+    float c[4];
+    height_point<float>(P, px, py, pz, c);
+    *reinterpret_cast<float4*>(coords + idx * 4) = make_float4(c[0], c[1], c[2], c[3]);
+  } else if (do_prep) {
     float c[3];
     preprocess_point(P, px, py, pz, c);
     coords[idx * 3 + 0] = c[0];
     coords[idx * 3 + 1] = c[1];
     coords[idx * 3 + 2] = c[2];
   }
+}
+
+__global__ void __launch_bounds__(256) sample_uniform_bins_kernel(
+    const float* __restrict__ origin, const float* __restrict__ dir,
+    const float* __restrict__ len, const float* __restrict__ u,
+    const float* __restrict__ bins, int64_t B, int32_t N, float* __restrict__ pts,
+    float* __restrict__ zout, PrepDev P, int do_prep, float* __restrict__ coords) {
+  sample_uniform_bins_body<false>(origin, dir, len, u, bins, B, N, pts, zout, P, do_prep, coords);
+}
+
+__global__ void __launch_bounds__(256) sample_uniform_bins_height_kernel(
+    const float* __restrict__ origin, const float* __restrict__ dir,
+    const float* __restrict__ len, const float* __restrict__ u,
+    const float* __restrict__ bins, int64_t B, int32_t N, float* __restrict__ pts,
+    float* __restrict__ zout, PrepDev P, float* __restrict__ coords) {
+  sample_uniform_bins_body<true>(origin, dir, len, u, bins, B, N, pts, zout, P, 1, coords);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) append_heights_kernel(
+    const T* __restrict__ pts, int64_t P_n, PrepDev P, float* __restrict__ out) {
+  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (idx >= P_n) return;
+  float c[4];
+  height_point<T>(P, pts[idx * 3 + 0], pts[idx * 3 + 1], pts[idx * 3 + 2], c);
+  *reinterpret_cast<float4*>(out + idx * 4) = make_float4(c[0], c[1], c[2], c[3]);
 }
 
 template <typename T>
@@ -296,17 +368,26 @@ extern "C" int anr_sample_uniform_bins(const float* origin, const float* dir,
   if (B == 0) return ANR_OK;
   PrepDev P{};
   if (prep) {
-    ANR_CHECK_ARG(prep->mode == 0 || prep->mode == 1, "anr_sample_uniform_bins: bad mode");
-    ANR_CHECK_ARG(prep->mode == 0 || (prep->lat_range != 0.0 && prep->lon_range != 0.0 &&
+    ANR_CHECK_ARG(prep->mode >= 0 && prep->mode <= 2, "anr_sample_uniform_bins: bad mode");
+    ANR_CHECK_ARG(prep->mode != 1 || (prep->lat_range != 0.0 && prep->lon_range != 0.0 &&
                                       prep->ray_origin_height != 0.0),
                   "anr_sample_uniform_bins: degenerate preprocessor ranges");
+    ANR_CHECK_ARG(prep->mode != 2 || (prep->ray_origin_height != 0.0 &&
+                                      (reinterpret_cast<uintptr_t>(coords) & 15) == 0),
+                  "anr_sample_uniform_bins: mode 2 needs ray_origin_height != 0 and 16-byte "
+                  "aligned (B,N,4) coords");
     P = make_prep(prep);
   }
   const int64_t total = B * N;
   const int threads = 256;
-  hipLaunchKernelGGL(sample_uniform_bins_kernel, dim3(ceil_div(total, threads)),
-                     dim3(threads), 0, as_stream(stream), origin, dir, len, u, bins, B, N,
-                     pts, z, P, prep ? 1 : 0, coords);
+  if (prep && prep->mode == 2)
+    hipLaunchKernelGGL(sample_uniform_bins_height_kernel, dim3(ceil_div(total, threads)),
+                       dim3(threads), 0, as_stream(stream), origin, dir, len, u, bins, B, N,
+                       pts, z, P, coords);
+  else
+    hipLaunchKernelGGL(sample_uniform_bins_kernel, dim3(ceil_div(total, threads)),
+                       dim3(threads), 0, as_stream(stream), origin, dir, len, u, bins, B, N,
+                       pts, z, P, prep ? 1 : 0, coords);
   ANR_CHECK_LAUNCH("anr_sample_uniform_bins");
   return ANR_OK;
 }
@@ -340,6 +421,37 @@ extern "C" int anr_preprocess_points_f64(const double* pts, int64_t P_n,
                      as_stream(stream), pts, P_n, P, coords);
   ANR_CHECK_LAUNCH("anr_preprocess_points_f64");
   return ANR_OK;
+}
+
+namespace anr {
+template <typename T>
+static int launch_append_heights(const T* pts, int64_t P_n, const anr_prep_params* prep,
+                                 float* out, anr_stream_t stream, const char* name) {
+  if (P_n == 0) return ANR_OK;
+  ANR_CHECK_ARG(pts && prep && out, "%s: null argument", name);
+  ANR_CHECK_ARG(P_n >= 0, "%s: negative size", name);
+  ANR_CHECK_ARG(prep->mode == 2 && prep->ray_origin_height != 0.0,
+                "%s: mode must be 2 with ray_origin_height != 0", name);
+  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "%s: out must be 16-byte aligned",
+                name);
+  const PrepDev P = make_prep(prep);
+  hipLaunchKernelGGL(append_heights_kernel<T>, dim3(ceil_div(P_n, 256)), dim3(256), 0,
+                     as_stream(stream), pts, P_n, P, out);
+  ANR_CHECK_LAUNCH(name);
+  return ANR_OK;
+}
+}  // namespace anr
+
+extern "C" int anr_append_heights(const float* pts, int64_t P_n, const anr_prep_params* prep,
+                                  float* out, anr_stream_t stream) {
+  return anr::launch_append_heights<float>(pts, P_n, prep, out, stream, "anr_append_heights");
+}
+
+extern "C" int anr_append_heights_f64(const double* pts, int64_t P_n,
+                                      const anr_prep_params* prep, float* out,
+                                      anr_stream_t stream) {
+  return anr::launch_append_heights<double>(pts, P_n, prep, out, stream,
+                                            "anr_append_heights_f64");
 }
 
 extern "C" int anr_preprocess_points_bwd(const float* pts, int64_t P, const anr_prep_params* prep,

@@ -29,7 +29,11 @@
 extern "C" {
 #endif
 
-/* ABI 5 (r06): anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and its workspace size;
+/* Added to ABI 5 without a version change (additive; every ABI 5 call behaves as it did):
+ * the include_height input -- 4-D hash grids (anr_hashgrid_init_nd; forward, backward and
+ * planes take its descriptors), anr_prep_params.mode 2 in anr_sample_uniform_bins ((B,N,4)
+ * coords), anr_append_heights and anr_append_heights_f64.
+ * ABI 5 (r06): anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and its workspace size;
  * added since without a version change (additive): anr_ingp_field_fwd_h,
  * anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16 interchange between the
  * field and the f16 composite).
@@ -60,7 +64,9 @@ const char* anr_last_error(void);
  * pipelines/instant_ngp.py:149,160.
  */
 typedef struct {
-  int32_t mode;            /* 0: no preprocessing (raw normalized xyz); 1: horizontal */
+  int32_t mode;            /* 0: no preprocessing (raw normalized xyz); 1: horizontal;
+                            * 2: raw xyz with the normalised ellipsoidal height appended
+                            * (include_height, samplers.py:168-195): 4-wide rows, see below */
   int32_t shift_lon;       /* dateline shift, harp2.py:366-370,379-380 */
   int32_t ngp_remap;       /* 1: out = (p+1)/2, out.z /= alt_compress (instant_ngp.py:149,160) */
   int32_t _pad;
@@ -77,7 +83,10 @@ typedef struct {
  *   midpoints (random=False, samplers.py:37-41); bins: (N+1,) f32 = torch.linspace(0,1,N+1).
  *   Outputs (each nullable): pts (B,N,3) f32 raw sample points (samplers.py:45);
  *   z (B,N) f32 (samplers.py:42); coords (B,N,3) f32 preprocessed (+remapped) points.
- *   z and pts are bit-identical to the reference for identical u (no FMA contraction). */
+ *   z and pts are bit-identical to the reference for identical u (no FMA contraction).
+ *   prep->mode 2 (include_height): coords is (B,N,4) f32, 16-byte aligned, rows
+ *   [x, y, z, h] as anr_append_heights writes them, computed where the sample sits in
+ *   registers. */
 int anr_sample_uniform_bins(const float* origin, const float* dir, const float* len,
                             const float* u, const float* bins, int64_t B, int32_t N,
                             float* pts, float* z, const anr_prep_params* prep,
@@ -93,6 +102,21 @@ int anr_preprocess_points(const float* pts, int64_t P, const anr_prep_params* pr
  * once, where tcnn casts the encoder input). */
 int anr_preprocess_points_f64(const double* pts, int64_t P, const anr_prep_params* prep,
                               float* coords, anr_stream_t stream);
+
+/* The Instant-NGP include_height input (instant_ngp.py:149-160,224-233): pts (P,3)
+ * -> out (P,4) f32 rows [x, y, z, h], out 16-byte aligned. prep->mode must be 2; scale,
+ * offset, ray_origin_height, ngp_remap and alt_compress are read. With ngp_remap the points
+ * are first remapped, p = (p + 1) / 2. h = f32(alt / ray_origin_height), alt the Bowring
+ * ellipsoidal height (wgs_84.py:83-97) of p * scale + offset formed in f64 from the REMAPPED
+ * points, as the reference's append_heights does (samplers.py:188); h is not confined to
+ * [0, 1]. With ngp_remap column 2 (alone) is then divided by alt_compress. Without
+ * ngp_remap this is samplers.append_heights on the points as given. _f64: remap and
+ * compression in f64, every column rounded to f32 once (the extract path). No backward:
+ * nothing in the Instant-NGP pipeline differentiates with respect to sample positions. */
+int anr_append_heights(const float* pts, int64_t P, const anr_prep_params* prep, float* out,
+                       anr_stream_t stream);
+int anr_append_heights_f64(const double* pts, int64_t P, const anr_prep_params* prep,
+                           float* out, anr_stream_t stream);
 
 /* Backward of the preprocessor (the NeRF pipeline back-propagates into the sample points,
  * harp2.py:372-386): d_pts (P,3) f32 WRITTEN = J^T d_coords, J from fp64 forward-mode
@@ -127,7 +151,7 @@ int anr_ingp_surface_input(const float* origin, const float* dir, const float* l
  * ------------------------------------------------------------------------------------ */
 #define ANR_MAX_LEVELS 32
 typedef struct {
-  int32_t n_dims;           /* 2 or 3 */
+  int32_t n_dims;           /* 2 or 3; 4 through anr_hashgrid_init_nd */
   int32_t n_levels;         /* <= ANR_MAX_LEVELS */
   int32_t n_features;       /* features per level: 1, 2, 4 or 8 */
   int32_t base_resolution;
@@ -143,6 +167,13 @@ typedef struct {
 int anr_hashgrid_init(anr_hashgrid_desc* d, int32_t n_dims, int32_t n_levels,
                       int32_t n_features, int32_t base_resolution, float per_level_scale,
                       int32_t log2_hashmap_size);
+
+/* The same for 2 to 4 dimensions. anr_hashgrid_init keeps refusing n_dims = 4, as it always
+ * has; the 4-D grid of include_height (instant_ngp.py:50) is asked for by name here. Every
+ * entry point below takes either descriptor. */
+int anr_hashgrid_init_nd(anr_hashgrid_desc* d, int32_t n_dims, int32_t n_levels,
+                         int32_t n_features, int32_t base_resolution, float per_level_scale,
+                         int32_t log2_hashmap_size);
 
 /* Forward: x (M, n_dims) f32 in [0,1] with row stride x_stride; table (n_params) in
  * table_dtype; out (M, n_levels*n_features) written at row stride out_stride
@@ -174,7 +205,8 @@ int64_t anr_hashgrid_bwd_chunk(int64_t M);
  * device) the memory-side requests the real launch makes: per flush instruction, the
  * distinct 64-B segments of its active lanes (zero-sum corners skipped as there).
  * bench.py's hash-backward roofline counts its benched step this way. 3-D, 2 features,
- * <= 16 levels; ANR_E_UNSUPPORTED otherwise. */
+ * <= 16 levels; ANR_E_UNSUPPORTED otherwise (2-D and 4-D grids included: their backward is
+ * not the v2 walker this models). */
 int anr_hashgrid_bwd_count_requests(const anr_hashgrid_desc* d, const float* x,
                                     int64_t x_stride, int64_t M, const void* dout,
                                     int32_t dout_dtype, int64_t dout_stride,
@@ -210,7 +242,7 @@ int anr_hashgrid_bwd_rows(const anr_hashgrid_desc* d, const float* x, int64_t x_
  * features as anr_hashgrid_fwd with f16 output, laid out as planes of four levels: level
  * l, feature f of row m at out[(l / 4) * plane_stride + 8 m + 2 (l % 4) + f]
  * (plane_stride >= 8 M f16 elements, multiple of 8; out 16-byte aligned; a partial last
- * quad is zero-filled). 2 features, <= 16 levels. The fused field kernels read this
+ * quad is zero-filled). 2 features, <= 16 levels, 2-D to 4-D. The fused field kernels read this
  * layout when given enc_stride = -plane_stride. Replaces the same call site as
  * anr_hashgrid_fwd (instant_ngp.py:163, the tcnn Encoding forward). */
 int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* x, int64_t x_stride,

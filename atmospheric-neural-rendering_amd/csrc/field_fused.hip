@@ -1122,7 +1122,8 @@ __device__ __forceinline__ h4 tr_b(h8 x, h8 sel) {
 // (a.loss_scale = 128) instead of the per-wavefront power of two, the ReLU masks test the
 // f16-rounded outputs, and the gradients that cross tinycudann module boundaries in the
 // reference are rounded as they are there: dL/dpos_out[1:16] comes back from dir_mlp /
-// dir_encoder as f16(f16(g_scaled) / 128) (a subnormal-flushing f16 division) and is
+// dir_encoder as f16(f16(g_scaled) / 128) (an f16 division that keeps subnormals, as
+// torch's does: tests/test_field_ref16_oracle_gpu.py) and is
 // rescaled for pos_mlp, and dL/denc is written as f16(f16(g_scaled) / 128)
 // (tinycudann/modules.py: input_grad / loss_scale, cast to the f16 input's dtype).
 // REF 2 (anr_ingp_field_bwd_ref16_rows): the same arithmetic, dL/denc written as f16 (its

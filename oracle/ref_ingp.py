@@ -235,6 +235,54 @@ class _TcnnCall(torch.autograd.Function):
         return gx, gp, None, None, None
 
 
+def _mlp_ref(x, p, n_in, n_out, width, n_hidden, acc, x_noise=None):
+    """FullyFusedMLP on f16 tiles: weights, activations and their gradients in f16; the
+    products in f64 or, with ``acc`` "f32" / "f32rev", in f32 (_MatmulAcc)."""
+    shapes, nip, _ = ref_tcnn.mlp_layer_shapes(n_in, n_out, int(width), int(n_hidden))
+    h = torch.cat([_RoundBoth.apply(x),
+                   torch.ones(x.shape[0], nip - n_in, dtype=torch.float64)], dim=1)
+    off = 0
+    for k, (o, i) in enumerate(shapes):
+        W = p[off:off + o * i].half().double().view(o, i)
+        off += o * i
+        h = h @ W.t() if acc == "f64" else _MatmulAcc.apply(h, W, acc == "f32rev")
+        if k < len(shapes) - 1:
+            # f16 tile: relu, rounded value and gradient, mask on the stored f16
+            # activation (tcnn's ReLU backward)
+            h = ref_tcnn.ReluRound.apply(h, torch.float16, True)
+            if x_noise is not None:
+                h = _GradNoise.apply(h, x_noise)
+    return h[:, :n_out]
+
+
+def field_reference(enc, dirs, n_per_ray, p_pos, p_dir, width, n_hidden_dir, n_out,
+                    acc="f64", n_hidden_pos=1, width_dir=None, x_noise=None):
+    """The per-sample field in reference semantics, one tinycudann module call each
+    (instant_ngp.py:164-184): pos_mlp (32 -> 16) -> cat[dirs, pos_out[:, 1:]] -> SH2 |
+    Identity -> dir_mlp (19 -> n_out) -> relu(color), relu(pos_out[:, 0]).
+
+    enc (M, 32) f16 (requires_grad for dL/denc), dirs (R, 3) f32 in [0, 1], one per
+    n_per_ray rows; p_pos / p_dir the flat parameter vectors (f64 leaves). Returns f16
+    sigma (M,) and color (M, n_out). ``torch.autograd.backward([color, sigma], [dc, ds])``
+    with f16 gradients leaves enc.grad = f16(f16(g_scaled) / 128) as f16 and the parameter
+    gradients f16(g_scaled) / 128 (_TcnnCall)."""
+    wd = width if width_dir is None else width_dir
+    pos_out = _TcnnCall.apply(enc, p_pos, lambda x, p: _mlp_ref(
+        x, p, 32, 16, width, n_hidden_pos, acc, x_noise), None, x_noise)
+    d = dirs[:, None].expand(dirs.shape[0], n_per_ray, 3).reshape(-1, 3).float()
+    # dir_encoder(cat[dirs, pos_out[:, 1:]]): the cat promotes to f32 (instant_ngp.py:
+    # 165-169); SH2 | Identity, f16 output; the identity part passes the gradient
+    x_dir = torch.cat([d, pos_out[:, 1:]], dim=1)
+
+    def dir_enc_fn(x, p):
+        sh = _sh2(x[:, :3])
+        return torch.cat([sh, x[:, 3:]], dim=1) + 0.0 * p.sum()
+    dir_enc = _TcnnCall.apply(x_dir, torch.zeros(1, dtype=torch.float64), dir_enc_fn)
+    color = _TcnnCall.apply(dir_enc, p_dir, lambda x, p: _mlp_ref(
+        x, p, 19, n_out, wd, n_hidden_dir, acc, x_noise), None, x_noise)
+    return torch.relu(pos_out[:, 0]), torch.relu(color)
+
+
 class RefInstantNGP:
     """Parameters (float64 leaf tensors, flat per module like tcnn) + forward / loss."""
 
@@ -317,24 +365,9 @@ class RefInstantNGP:
 
     # ------------------------------------------------------------ reference semantics
     def _mlp_ref(self, x, p, n_in, n_out, net_cfg):
-        """FullyFusedMLP on f16 tiles: weights, activations and their gradients in f16."""
-        shapes, nip, _ = ref_tcnn.mlp_layer_shapes(n_in, n_out, int(net_cfg["n_neurons"]),
-                                                   int(net_cfg["n_hidden_layers"]))
-        h = torch.cat([_RoundBoth.apply(x),
-                       torch.ones(x.shape[0], nip - n_in, dtype=torch.float64)], dim=1)
-        off = 0
-        for k, (o, i) in enumerate(shapes):
-            W = p[off:off + o * i].half().double().view(o, i)
-            off += o * i
-            h = h @ W.t() if self.acc == "f64" else _MatmulAcc.apply(h, W, self.acc == "f32rev")
-            if k < len(shapes) - 1:
-                # f16 tile: relu, rounded value and gradient, mask on the stored f16
-                # activation (tcnn's ReLU backward)
-                h = ref_tcnn.ReluRound.apply(h, torch.float16, True)
-                xn = getattr(self, "mlp_x_noise", None)
-                if xn is not None:
-                    h = _GradNoise.apply(h, xn)
-        return h[:, :n_out]
+        return _mlp_ref(x, p, n_in, n_out, int(net_cfg["n_neurons"]),
+                        int(net_cfg["n_hidden_layers"]), self.acc,
+                        getattr(self, "mlp_x_noise", None))
 
     def _grid_ref(self, cfg):
         def fn(x, p):
@@ -353,19 +386,12 @@ class RefInstantNGP:
                                   self._grid_ref(self.pos_grid),
                                   getattr(self, "grid_sum_noise", None))
         xn = getattr(self, "mlp_x_noise", None)
-        pos_out = _TcnnCall.apply(pos_enc, P["pos_mlp"], lambda x, p: self._mlp_ref(
-            x, p, 32, 16, ing["network"]), None, xn)
-        dirs = b["dir"][:, None].expand(B, N, 3).reshape(B * N, 3).float()
-        # dir_encoder(cat[dirs, pos_out[:, 1:]]): the cat promotes to f32 (instant_ngp.py:
-        # 165-169); SH2 | Identity, f16 output; the identity part passes the gradient
-        x_dir = torch.cat([dirs, pos_out[:, 1:]], dim=1)
-
-        def dir_enc_fn(x, p):
-            sh = _sh2(x[:, :3])
-            return torch.cat([sh, x[:, 3:]], dim=1) + 0.0 * p.sum()
-        dir_enc = _TcnnCall.apply(x_dir, torch.zeros(1, dtype=torch.float64), dir_enc_fn)
-        color = _TcnnCall.apply(dir_enc, P["dir_mlp"], lambda x, p: self._mlp_ref(
-            x, p, 19, self.nb, ing["rgb_network"]), None, xn)
+        net, rgb = ing["network"], ing["rgb_network"]
+        sigma, color = field_reference(
+            pos_enc, b["dir"].float(), N, P["pos_mlp"], P["dir_mlp"], int(net["n_neurons"]),
+            int(rgb["n_hidden_layers"]), self.nb, self.acc,
+            n_hidden_pos=int(net["n_hidden_layers"]), width_dir=int(rgb["n_neurons"]),
+            x_noise=xn)
         ps = ((b["origin"] + b["dir"] * b["len"][:, None] + 1) / 2).float()
         surf_in = torch.cat([ps[:, :2], b["dir"].float()], dim=1)
         surf_grid = self._grid_ref(self.surf_grid)
@@ -375,9 +401,9 @@ class RefInstantNGP:
         surf_enc = _TcnnCall.apply(surf_in, P["surf_encoder"], surf_enc_fn)
         color_surf = _TcnnCall.apply(surf_enc, P["surf_mlp"], lambda x, p: self._mlp_ref(
             x, p, 36, self.nb, ing["surface_network"]), None, xn)
-        color = torch.relu(color.view(B, N, -1))
+        color = color.view(B, N, -1)
         color_surf = torch.relu(color_surf)
-        sigma = torch.relu(pos_out[:, :1]).view(B, N, 1)
+        sigma = sigma.view(B, N, 1)
         render = (ref_path.render_with_surface if self.ref_acc == "cpu" else
                   lambda *a: ref_f16.render_with_surface(*a, acc=self.ref_acc))
         cm, alpha, weights, atmo, surf = render(

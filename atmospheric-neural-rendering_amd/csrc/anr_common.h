@@ -7,6 +7,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "../../include/anr.h"
 
 namespace anr {
@@ -36,6 +39,31 @@ inline hipStream_t as_stream(anr_stream_t s) { return reinterpret_cast<hipStream
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 constexpr int kWave = 64;  // CDNA wavefront width
+
+// ---------------------------------------------------------------- launch geometry
+// Blocks of kernel `fn` that one CU holds at once, at `threads` per block and `lds` bytes
+// of dynamic LDS. Queried once per kernel; a failed query counts as 1.
+inline int blocks_per_cu(const void* fn, int threads, size_t lds = 0) {
+  static std::mutex mu;
+  static std::unordered_map<const void*, int> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  int& per_cu = cache[fn];
+  if (per_cu == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds) != hipSuccess || nb < 1)
+      nb = 1;
+    per_cu = nb;
+  }
+  return per_cu;
+}
+
+// Grid of a persistent kernel: a block per `work_blocks` up to what the chip's 256 CUs hold
+// at once, and at least one.
+inline int64_t persistent_blocks(int64_t work_blocks, int per_cu) {
+  const int64_t cap = 256LL * per_cu;
+  const int64_t blocks = work_blocks < cap ? work_blocks : cap;
+  return blocks < 1 ? 1 : blocks;
+}
 
 // ---------------------------------------------------------------- dtype helpers
 template <typename T>

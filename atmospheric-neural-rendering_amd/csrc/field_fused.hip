@@ -1736,60 +1736,34 @@ static int g_fwd_ut = 1;
 struct BwdGeom {
   int64_t blocks, nw, tpw;
 };
-template <int W, int NHD, bool BF>
-static const void* bwd_fn(bool fast) {
-  return fast ? reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, BF>)
-              : reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, false, false, BF>);
-}
-template <int W, int NHD, bool BF>
-static BwdGeom bwd_geom(int64_t M, bool fast) {
+// the grid of a 4-wave kernel with `per_cu` resident blocks per CU over M rows
+static BwdGeom tile_geom(int64_t M, int per_cu) {
   const int waves = 4;
-  static int pc[2] = {0, 0};
-  int& p = pc[fast ? 1 : 0];
-  if (p == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, bwd_fn<W, NHD, BF>(fast), 64 * waves, 0) != hipSuccess || nb < 1) nb = 1;
-    p = nb;
-  }
   const int64_t tiles = (M + 31) / 32;
-  int64_t blocks = (tiles + waves - 1) / waves;
-  if (blocks > 256LL * p) blocks = 256LL * p;
-  if (blocks < 1) blocks = 1;
+  const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, per_cu);
   const int64_t nw = blocks * waves;
   return {blocks, nw, (tiles + nw - 1) / nw};
+}
+// every backward form of one d_color layout (fast or general) runs the grid of its plain
+// (REF 0, f32-gradient) instantiation
+template <int W, int NHD, bool BF>
+static BwdGeom bwd_geom(int64_t M, bool fast) {
+  const void* fn = fast ? reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, BF>)
+                        : reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, false, false, BF>);
+  return tile_geom(M, blocks_per_cu(fn, 256));
 }
 
 // the reference-numerics pos pass (REF 4): its own occupancy (no dir network's registers
 // or LDS sums); the list pass (REF 3): one block per CU slot of its occupancy
 template <int W, int NHD, bool HG>
 static BwdGeom pos_geom(int64_t M) {
-  const int waves = 4;
-  static int p = 0;
-  if (p == 0) {
-    int nb = 0;
-    const void* fn =
-        reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 4, HG>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, 0) != hipSuccess || nb < 1) nb = 1;
-    p = nb;
-  }
-  const int64_t tiles = (M + 31) / 32;
-  int64_t blocks = (tiles + waves - 1) / waves;
-  if (blocks > 256LL * p) blocks = 256LL * p;
-  if (blocks < 1) blocks = 1;
-  const int64_t nw = blocks * waves;
-  return {blocks, nw, (tiles + nw - 1) / nw};
+  const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 4, HG>);
+  return tile_geom(M, blocks_per_cu(fn, 256));
 }
 template <int W, int NHD, bool HG>
 static int64_t list_blocks() {
-  static int p = 0;
-  if (p == 0) {
-    int nb = 0;
-    const void* fn =
-        reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 3, HG>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, 0) != hipSuccess || nb < 1) nb = 1;
-    p = nb;
-  }
-  return 256LL * p;
+  const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 3, HG>);
+  return 256LL * blocks_per_cu(fn, 256);
 }
 
 template <int W, int NHD, bool BF>
@@ -1811,16 +1785,10 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
   const int waves = 4;
   if (op == 1) {
     const int64_t tiles = (a.M + 15) / 16;
+    // every forward form runs the grid of the general f32 one
     const void* fn = reinterpret_cast<const void*>(&fwd_kernel<W, NHD, false, BF, false>);
-    static int pc = 0;
-    if (pc == 0) {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, 0) != hipSuccess || nb < 1) nb = 1;
-      pc = nb;
-    }
-    int64_t blocks = (tiles + waves - 1) / waves;
-    if (blocks > 256LL * pc) blocks = 256LL * pc;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks =
+        persistent_blocks((tiles + waves - 1) / waves, blocks_per_cu(fn, 64 * waves));
     // the uniform-tile form (see fwd_kernel): dense rows whose 16-row tiles are one ray each,
     // 4 colour outputs in 16-byte aligned rows, byte offsets of the outputs below 2^31
     const bool ho = a.color_h != nullptr;  // f16 outputs (same grid as the f32 form)
@@ -1845,9 +1813,8 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
   }
   if (op == 3) {
     const int64_t tiles = (a.M + 15) / 16;
-    int64_t blocks = (tiles + waves - 1) / waves;
-    if (blocks > 256LL * 8) blocks = 256LL * 8;  // 8 blocks (32 waves) per CU, grid-stride
-    if (blocks < 1) blocks = 1;
+    // 8 blocks (32 waves) per CU, grid-stride
+    const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, 8);
     hipLaunchKernelGGL((density_kernel<W, NHD, BF>), dim3(blocks), dim3(64 * waves), 0, st, a);
     return 0;
   }
@@ -1959,48 +1926,19 @@ static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
 // as fit on the chip at once (the occupancy query), each wavefront walking 64-sample
 // segments grid-stride
 constexpr int HF_WAVES = 8;
-// register cap (waves per SIMD) of the fused forward, ANR_HF_OCC = 4 / 5 / 6, and its
-// run-leader gathers, ANR_HF_DEDUP = 0 / 1 (A/B hooks)
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-static int hf_occ() {
-  static const int v = env_int("ANR_HF_OCC", 6);
-  return v;
-}
-static bool hf_dedup() {
-  static const bool v = env_int("ANR_HF_DEDUP", 0) != 0;
-  return v;
-}
-template <int W, int NHD, bool BF, int OCC, int DD>
-static int launch_hf(const Args& a, const HashArgs& h, hipStream_t st) {
-  const void* fn = reinterpret_cast<const void*>(&hf_fwd_kernel<W, NHD, BF, HF_WAVES, OCC, DD>);
-  static int pc = 0;
-  if (pc == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * HF_WAVES, 0) != hipSuccess || nb < 1) nb = 1;
-    pc = nb;
-  }
-  const int64_t n_super = (a.M + 63) / 64;
-  int64_t blocks = (n_super + HF_WAVES - 1) / HF_WAVES;
-  if (blocks > 256LL * pc) blocks = 256LL * pc;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((hf_fwd_kernel<W, NHD, BF, HF_WAVES, OCC, DD>), dim3(blocks),
-                     dim3(64 * HF_WAVES), 0, st, a, h);
-  return 0;
-}
-template <int W, int NHD, bool BF, int DD>
-static int run_hf_dd(const Args& a, const HashArgs& h, hipStream_t st) {
-  switch (hf_occ()) {
-    case 4: return launch_hf<W, NHD, BF, 4, DD>(a, h, st);
-    case 5: return launch_hf<W, NHD, BF, 5, DD>(a, h, st);
-    default: return launch_hf<W, NHD, BF, 6, DD>(a, h, st);
-  }
-}
+// register cap of the fused forward: 6 waves per SIMD. It runs without run-leader gathers
+// (DEDUP 0): with them it measured 0.74-0.79 ms at caps of 4, 5 and 6 against 0.64-0.65 ms
+// without (profiles/r06_hash_field_fwd_variants.log).
+constexpr int HF_OCC = 6;
 template <int W, int NHD, bool BF>
 static int run_hf(const Args& a, const HashArgs& h, hipStream_t st) {
-  return hf_dedup() ? run_hf_dd<W, NHD, BF, HASH_DEDUP>(a, h, st) : run_hf_dd<W, NHD, BF, 0>(a, h, st);
+  const void* fn = reinterpret_cast<const void*>(&hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>);
+  const int64_t n_super = (a.M + 63) / 64;
+  const int64_t blocks = persistent_blocks((n_super + HF_WAVES - 1) / HF_WAVES,
+                                           blocks_per_cu(fn, 64 * HF_WAVES));
+  hipLaunchKernelGGL((hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>), dim3(blocks),
+                     dim3(64 * HF_WAVES), 0, st, a, h);
+  return 0;
 }
 template <bool BF>
 static int dispatch_hf_t(int v, const Args& a, const HashArgs& h, hipStream_t st) {

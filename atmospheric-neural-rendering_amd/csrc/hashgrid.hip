@@ -938,25 +938,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
 // K = 512 makes the STEP slower (3.227 / 3.228 ms at 256 vs 3.270 / 3.267 at 512, alternating
 // runs on one box, hash bwd 1.139 vs 1.129 ms: profiles/r04_hash_bwd_k_step_ab.log). Rule:
 // 256 samples per chunk down to 4,096 chunks, shorter below that.
-static int64_t env_k(const char* name) {
-  const char* e = getenv(name);  // profiling override of the chunk length
-  return e ? atoll(e) : 0;
-}
-// run-leader gathers in the planes forward (plane_quad): ANR_HASH_DEDUP = the largest
-// number of cell changes per wavefront at which a level gathers at the run leaders only
-// (0 = off, 16 / 32 / 48 / 64; A/B hook, default HASH_DEDUP = 64: every level. Measured on
-// the settled bench step, hash fwd 0.478 ms off, 0.435 / 0.439 / 0.433 / 0.421 ms at
-// 32 / 16 / 48 / 64: profiles/r06_hash_fwd_dedup_sweep.log)
-static int plane_dedup() {
-  static const int v = [] {
-    const char* e = getenv("ANR_HASH_DEDUP");
-    return e ? atoi(e) : HASH_DEDUP;
-  }();
-  return v;
-}
 static int64_t pick_chunk_v2(int64_t M) {
-  static const int64_t over = env_k("ANR_HASH_KB");
-  if (over > 0) return over;
   int64_t K = M / 4096;
   if (K < 1) K = 1;
   if (K > 256) K = 256;
@@ -967,28 +949,24 @@ static int64_t pick_chunk_v2(int64_t M) {
 // fastest on the ray-coherent bench workload; v6 falls back to v1 above 16 levels or
 // past 32-bit buffer offsets); 1: both v1 (the generic kernels every shape falls back
 // to); 6: forward v1, backward v2 (the r01 default); 7: as 0 with the backward's run-time-
-// stride instantiation (A/B of the compile-time strides). ANR_HASHGRID_MODE or
-// anr_hashgrid_force_v1() selects it (test hook). The r02 forward experiments v2-v5
+// stride instantiation (A/B of the compile-time strides). anr_hashgrid_force_v1() selects
+// it (test hook). The r02 forward experiments v2-v5
 // (x-pair lanes, batched gathers, one thread per sample, LDS-compacted gathers) measured
 // slower than v6 and were removed in r04 (profiles/r02_hash_fwd_v6_v7_ab.log). On the
 // bench coordinates the forward spends ~0.35 of its ~0.65 ms on the corner gathers' memory
 // traffic (0.29 ms with no gathers at all) and is not issue-bound.
 static bool valid_mode(int m) { return m == 0 || m == 1 || m == 6 || m == 7; }
-static int g_hashgrid_mode = [] {
-  const char* e = getenv("ANR_HASHGRID_MODE");
-  return (e && e[0] >= '0' && e[0] <= '9' && valid_mode(e[0] - '0')) ? e[0] - '0' : 0;
-}();
+static int g_hashgrid_mode = 0;
 static bool fwd_v6() { return g_hashgrid_mode == 0 || g_hashgrid_mode == 7; }
 static bool bwd_v2() { return g_hashgrid_mode != 1; }
 
-// Levels per wavefront of the forward walker (1, 2, 4, 8, 16, 32 or 64).
-static int fwd_lpw() {
-  static const int v = [] {
-    const char* e = getenv("ANR_HASH_LPW");  // profiling override
-    const int k = e ? atoi(e) : 0;
-    return (k >= 1 && k <= 64 && (64 % k) == 0) ? k : 16;
-  }();
-  return v;
+// Levels per wavefront of the v1 forward walker (the kernel takes 1, 2, 4, 8, 16, 32 or 64):
+// 8 / 32 measured 0.99 / 0.81 ms against 0.65 ms at 16 on the bench coordinates.
+constexpr int kFwdLpw = 16;
+
+// Bytes of a table over all levels, at `entry_bytes` (features x element size) per entry.
+static int64_t table_bytes(const GridLevels& G, int n_levels, int64_t entry_bytes) {
+  return (static_cast<int64_t>(G.offset[n_levels - 1]) + G.size[n_levels - 1]) * entry_bytes;
 }
 
 // Samples per chunk: long chunks amortise the per-cell gathers/atomics, but the grid
@@ -1000,8 +978,6 @@ static int fwd_lpw() {
 // ended or began mid-column every time: 0.782 ms per 2.65 M points against 0.412 ms with
 // 81-point chunks (profiles/r04_extract_chunk_sweep.log).
 static int64_t pick_chunk(int64_t M, int64_t run = 0) {
-  static const int64_t over = env_k("ANR_HASH_KF");
-  if (over > 0) return over;
   if (run > 0 && run <= 256) return run;
   int64_t K = M / 65536;
   if (K < 1) K = 1;
@@ -1020,7 +996,7 @@ static int launch_fwd(const GridLevels& G, const anr_hashgrid_desc* d, const flo
     // 32-bit buffer offsets: every byte range must stay below 2^31
     const int64_t esz_t = tdt == ANR_F16 ? 2 : 4, esz_o = odt == ANR_F16 ? 2 : 4;
     const int64_t x_bytes = ((M - 1) * x_stride + D) * 4;
-    const int64_t t_bytes = static_cast<int64_t>(G.offset[d->n_levels - 1] + G.size[d->n_levels - 1]) * 2 * esz_t;
+    const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * esz_t);
     const int64_t o_bytes = ((M - 1) * out_stride + d->n_levels * 2) * esz_o;
     const int64_t K = pick_chunk(M, run);
     const int64_t lim = int64_t(1) << 31;
@@ -1043,7 +1019,7 @@ static int launch_fwd(const GridLevels& G, const anr_hashgrid_desc* d, const flo
       return ANR_OK;
     }
   }
-  const int lpw = fwd_lpw();
+  const int lpw = kFwdLpw;
   const int n_groups = static_cast<int>(ceil_div(d->n_levels, lpw));
   const int64_t K = pick_chunk(M, run);
   const int64_t chunks = ceil_div(M, K);
@@ -1067,45 +1043,56 @@ static int launch_fwd(const GridLevels& G, const anr_hashgrid_desc* d, const flo
 // reference numerics most samples' f16 dL/denc underflow to zero (tcnn's x128 loss scale
 // rounds them away), and the memory-side request count at the chunk ends alone fell from
 // 20.8 M to 18.7 M per launch after the first step (profiles/r04_close PMC).
-// ANR_HASH_SKIP0 = 0 / 1 / 2 overrides (A/B hook); default 2 (per-sample skip of
-// all-zero dL/dy rows, r05).
-static int bwd_skip_zero() {
-  static const int v = [] {
-    const char* e = getenv("ANR_HASH_SKIP0");
-    const int k = e ? atoi(e) : 2;
-    return k < 0 ? 0 : (k > 2 ? 2 : k);
-  }();
-  return v;
+// The kernel's skip_zero argument takes 0 (off), 1 (the cell-move flushes) or 2 (also a
+// per-sample skip of all-zero dL/dy rows, r05); every launch passes 2.
+constexpr int kBwdSkipZero = 2;
+
+// The v2 backward walker's grids: 2 features, at most 16 levels, 2-D or 3-D (LaneCorners,
+// its corner carry, has no 4-D form), and not switched off by anr_hashgrid_force_v1 ...
+static bool bwd_v2_shape(const anr_hashgrid_desc* d) {
+  return d->n_features == 2 && d->n_dims <= 3 && d->n_levels <= 16 && bwd_v2();
+}
+// ... and a gradient table below 2 GB: v2 addresses it through a buffer descriptor (32-bit
+// byte offsets, the drop offset at 2 GB), so larger tables (2^24 entries x 16 levels) take
+// the v1 walker
+static bool bwd_v2_takes(const anr_hashgrid_desc* d, const GridLevels& G) {
+  return bwd_v2_shape(d) && table_bytes(G, d->n_levels, 2 * 4) < (int64_t{1} << 31);
+}
+
+// One launch of the v2 walker over chunks of K rows, a chunk per wavefront, dL/dy in f16 or
+// f32. XS, DS: compile-time strides (0: the run-time ones).
+template <int D, int XS, int DS, bool COUNT = false, int BSZ = HASH_BS, bool SPARSE = false>
+static void launch_bwd_v2(const GridLevels& G, const anr_hashgrid_desc* d, const float* x,
+                          int64_t x_stride, int64_t M, int64_t K, const void* dout, int32_t gdt,
+                          int64_t dout_stride, float* dtable, hipStream_t s,
+                          unsigned long long* count = nullptr, const uint8_t* tile_nz = nullptr,
+                          const uint32_t* row_nz = nullptr) {
+  const dim3 grid(static_cast<unsigned>(ceil_div(ceil_div(M, K), 4))), block(256);
+  if (gdt == ANR_F16)
+    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, __half, XS, DS, COUNT, BSZ, SPARSE>), grid,
+                       block, 0, s, G, d->n_levels, x, x_stride, M, K,
+                       static_cast<const __half*>(dout), dout_stride, dtable, kBwdSkipZero, count,
+                       tile_nz, row_nz);
+  else
+    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, float, XS, DS, COUNT, BSZ, SPARSE>), grid,
+                       block, 0, s, G, d->n_levels, x, x_stride, M, K,
+                       static_cast<const float*>(dout), dout_stride, dtable, kBwdSkipZero, count,
+                       tile_nz, row_nz);
 }
 
 template <int D, int F>
 static int launch_bwd(const GridLevels& G, const anr_hashgrid_desc* d, const float* x,
                       int64_t x_stride, int64_t M, const void* dout, int32_t gdt,
                       int64_t dout_stride, float* dtable, hipStream_t s) {
-  // v2 addresses the gradient table through a buffer descriptor (32-bit byte offsets, the
-  // drop offset at 2 GB): larger tables (2^24 entries x 16 levels) take the v1 walker
-  const uint64_t grad_bytes =
-      (static_cast<uint64_t>(G.offset[d->n_levels - 1]) + G.size[d->n_levels - 1]) * F * 4u;
-  // 4-D runs the generic v1 walker (LaneCorners, the v2 walker's corner carry, is 2-D / 3-D)
+  // every other grid runs the generic v1 walker
   if constexpr (F == 2 && D <= 3)
-  if (d->n_levels <= 16 && grad_bytes < 0x80000000ull && bwd_v2()) {
+  if (bwd_v2_takes(d, G)) {
     const int64_t K = pick_chunk_v2(M);
-    const int64_t waves = ceil_div(M, K);
-    const dim3 grid(static_cast<unsigned>(ceil_div(waves, 4))), block(256);
     // compile-time strides for the fused field's layout ((M,3) coordinates, (M,32) dL/denc)
-    const bool fixed = D == 3 && x_stride == 3 && dout_stride == 32 && g_hashgrid_mode != 7;
-#define ANR_HG_BWD2(TG, XS_, DS_)                                                          \
-  hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, TG, XS_, DS_>), grid, block, 0, s, G,        \
-                     d->n_levels, x, x_stride, M, K, static_cast<const TG*>(dout),          \
-                     dout_stride, dtable, bwd_skip_zero())
-    if (gdt == ANR_F16) {
-      if (fixed) ANR_HG_BWD2(__half, 3, 32);
-      else ANR_HG_BWD2(__half, 0, 0);
-    } else {
-      if (fixed) ANR_HG_BWD2(float, 3, 32);
-      else ANR_HG_BWD2(float, 0, 0);
-    }
-#undef ANR_HG_BWD2
+    if (D == 3 && x_stride == 3 && dout_stride == 32 && g_hashgrid_mode != 7)
+      launch_bwd_v2<D, 3, 32>(G, d, x, x_stride, M, K, dout, gdt, dout_stride, dtable, s);
+    else
+      launch_bwd_v2<D, 0, 0>(G, d, x, x_stride, M, K, dout, gdt, dout_stride, dtable, s);
     ANR_CHECK_LAUNCH("anr_hashgrid_bwd(v2)");
     return ANR_OK;
   }
@@ -1234,34 +1221,24 @@ extern "C" int anr_hashgrid_bwd_count_requests(const anr_hashgrid_desc* d, const
                 "anr_hashgrid_bwd_count_requests: bad shape/stride");
   ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32,
                 "anr_hashgrid_bwd_count_requests: bad dtype");
-  if (!(d->n_dims == 3 && d->n_features == 2 && d->n_levels <= 16 && bwd_v2())) {
+  if (!(d->n_dims == 3 && bwd_v2_shape(d))) {
     set_error("anr_hashgrid_bwd_count_requests: only the v2 backward (3-D, 2 features, <= 16 "
               "levels) is instrumented");
     return ANR_E_UNSUPPORTED;
   }
   GridLevels G;
   ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_count_requests: descriptor not initialised");
-  // the same gate as launch_bwd: gradient tables of 2 GB or more take the v1 walker there,
-  // whose requests this v2 instrument does not model
-  const uint64_t grad_bytes =
-      (static_cast<uint64_t>(G.offset[d->n_levels - 1]) + G.size[d->n_levels - 1]) * 2u * 4u;
-  if (grad_bytes >= 0x80000000ull) {
+  // gradient tables of 2 GB or more take the v1 walker in launch_bwd, whose requests this
+  // v2 instrument does not model
+  if (!bwd_v2_takes(d, G)) {
     set_error("anr_hashgrid_bwd_count_requests: gradient table of 2 GB or more (the backward "
               "runs the uninstrumented v1 walker there)");
     return ANR_E_UNSUPPORTED;
   }
   if (M == 0) return ANR_OK;
-  const int64_t K = pick_chunk_v2(M);
-  const dim3 grid(static_cast<unsigned>(ceil_div(ceil_div(M, K), 4))), block(256);
   float* tab = const_cast<float*>(dtable);  // not written in COUNT mode
-  if (dout_dtype == ANR_F16)
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, __half, 0, 0, true>), grid, block, 0,
-                       as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const __half*>(dout), dout_stride, tab, bwd_skip_zero(), count);
-  else
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, float, 0, 0, true>), grid, block, 0,
-                       as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const float*>(dout), dout_stride, tab, bwd_skip_zero(), count);
+  launch_bwd_v2<3, 0, 0, true>(G, d, x, x_stride, M, pick_chunk_v2(M), dout, dout_dtype,
+                               dout_stride, tab, as_stream(stream), count);
   ANR_CHECK_LAUNCH("anr_hashgrid_bwd_count_requests");
   return ANR_OK;
 }
@@ -1321,41 +1298,31 @@ extern "C" int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* 
   const int64_t esz_t = table_dtype == ANR_F16 ? 2 : 4;
   const int64_t n_quads = (d->n_levels + 3) / 4;
   const int64_t x_bytes = ((M - 1) * x_stride + d->n_dims) * 4;
-  const int64_t t_bytes =
-      static_cast<int64_t>(G.offset[d->n_levels - 1] + G.size[d->n_levels - 1]) * 2 * esz_t;
+  const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * esz_t);
   const int64_t o_bytes = ((n_quads - 1) * plane_stride + 8 * M) * 2;
   const int64_t lim = int64_t(1) << 31;
   ANR_CHECK_ARG(x_bytes < lim && t_bytes < lim && o_bytes < lim &&
                     (M + 256) * x_stride * 4 < lim && plane_stride * 2 < lim,
                 "anr_hashgrid_fwd_planes: byte ranges must stay below 2^31");
   const dim3 grid(static_cast<unsigned>(ceil_div(M, 256))), block(256);
-  const int dd = plane_dedup();
-#define ANR_HG_PL(D_, TT)                                                                    \
-  do {                                                                                       \
-    switch (dd) {                                                                            \
-      case 0: ANR_HG_PL1(D_, TT, 0); break;                                                  \
-      case 16: ANR_HG_PL1(D_, TT, 16); break;                                                \
-      case 48: ANR_HG_PL1(D_, TT, 48); break;                                                \
-      case 32: ANR_HG_PL1(D_, TT, 32); break;                                                \
-      default: ANR_HG_PL1(D_, TT, HASH_DEDUP); break;                                        \
-    }                                                                                        \
-  } while (0)
-#define ANR_HG_PL1(D_, TT, DD)                                                               \
-  hipLaunchKernelGGL((hashgrid_fwd_planes_kernel<D_, TT, DD>), grid, block, 0, as_stream(stream), \
-                     G, d->n_levels, x, static_cast<uint32_t>(x_bytes),                      \
+  // run-leader gathers (plane_quad) at every level, HASH_DEDUP = 64: the largest number of
+  // cell changes per wavefront at which a level gathers at the run leaders only. Measured on
+  // the settled bench step, hash fwd 0.478 ms with them off, 0.435 / 0.439 / 0.433 / 0.421 ms
+  // at 32 / 16 / 48 / 64 (profiles/r06_hash_fwd_dedup_sweep.log)
+#define ANR_HG_PL1(D_, TT)                                                                   \
+  hipLaunchKernelGGL((hashgrid_fwd_planes_kernel<D_, TT, HASH_DEDUP>), grid, block, 0,       \
+                     as_stream(stream), G, d->n_levels, x, static_cast<uint32_t>(x_bytes),   \
                      static_cast<uint32_t>(x_stride * 4), M, static_cast<const TT*>(table),  \
                      static_cast<uint32_t>(t_bytes), static_cast<__half*>(out),              \
                      static_cast<uint32_t>(o_bytes), static_cast<uint32_t>(plane_stride * 2))
-  if (d->n_dims == 4) {
-    if (table_dtype == ANR_F16) ANR_HG_PL(4, __half);
-    else ANR_HG_PL(4, float);
-  } else if (d->n_dims == 3) {
-    if (table_dtype == ANR_F16) ANR_HG_PL(3, __half);
-    else ANR_HG_PL(3, float);
-  } else {
-    if (table_dtype == ANR_F16) ANR_HG_PL(2, __half);
-    else ANR_HG_PL(2, float);
-  }
+#define ANR_HG_PL(D_)                                                                        \
+  do {                                                                                       \
+    if (table_dtype == ANR_F16) ANR_HG_PL1(D_, __half);                                      \
+    else ANR_HG_PL1(D_, float);                                                              \
+  } while (0)
+  if (d->n_dims == 4) ANR_HG_PL(4);
+  else if (d->n_dims == 3) ANR_HG_PL(3);
+  else ANR_HG_PL(2);
 #undef ANR_HG_PL
 #undef ANR_HG_PL1
   ANR_CHECK_LAUNCH("anr_hashgrid_fwd_planes");
@@ -1375,25 +1342,14 @@ extern "C" int anr_hashgrid_bwd_tiles(const anr_hashgrid_desc* d, const float* x
   ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32, "anr_hashgrid_bwd_tiles: bad dtype");
   GridLevels G;
   ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_tiles: descriptor not initialised");
-  const uint64_t grad_bytes =
-      (static_cast<uint64_t>(G.offset[d->n_levels - 1]) + G.size[d->n_levels - 1]) * 2u * 4u;
   const int64_t K = pick_chunk_v2(M);
-  if (!(d->n_dims == 3 && d->n_features == 2 && d->n_levels <= 16 && bwd_v2() &&
-        grad_bytes < 0x80000000ull && K % 32 == 0 && x_stride == 3 && dout_stride == 32)) {
+  if (!(d->n_dims == 3 && bwd_v2_takes(d, G) && K % 32 == 0 && x_stride == 3 &&
+        dout_stride == 32)) {
     // outside the tiled walker's shapes: the flags are an optimisation only
     return anr_hashgrid_bwd(d, x, x_stride, M, dout, dout_dtype, dout_stride, dtable, stream);
   }
-  const dim3 grid(static_cast<unsigned>(ceil_div(ceil_div(M, K), 4))), block(256);
-  if (dout_dtype == ANR_F16)
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, __half, 3, 32, false, 8>), grid, block, 0,
-                       as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const __half*>(dout), dout_stride, dtable, bwd_skip_zero(),
-                       nullptr, tile_nz);
-  else
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, float, 3, 32, false, 8>), grid, block, 0,
-                       as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const float*>(dout), dout_stride, dtable, bwd_skip_zero(),
-                       nullptr, tile_nz);
+  launch_bwd_v2<3, 3, 32, false, 8>(G, d, x, x_stride, M, K, dout, dout_dtype, dout_stride,
+                                    dtable, as_stream(stream), nullptr, tile_nz);
   ANR_CHECK_LAUNCH("anr_hashgrid_bwd_tiles");
   return ANR_OK;
 }
@@ -1426,15 +1382,12 @@ extern "C" int anr_hashgrid_bwd_rows(const anr_hashgrid_desc* d, const float* x,
   ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32, "anr_hashgrid_bwd_rows: bad dtype");
   GridLevels G;
   ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_rows: descriptor not initialised");
-  const uint64_t grad_bytes =
-      (static_cast<uint64_t>(G.offset[d->n_levels - 1]) + G.size[d->n_levels - 1]) * 2u * 4u;
   // chunks of whole 32-row words (the rule's length rounded down, at least one word)
   int64_t K = pick_chunk_v2(M) / 32 * 32;
   if (K < 32) K = 32;
   if (K > 256) K = 256;
-  if (!(d->n_dims == 3 && d->n_features == 2 && d->n_levels == 16 && bwd_v2() &&
-        grad_bytes < 0x80000000ull && x_stride == 3 && dout_stride == 32 &&
-        M < (int64_t{1} << 31))) {
+  if (!(d->n_dims == 3 && bwd_v2_takes(d, G) && d->n_levels == 16 && x_stride == 3 &&
+        dout_stride == 32 && M < (int64_t{1} << 31))) {
     // outside the row-mask walker's shapes: the clear rows are zeroed in place, then the
     // dense walker reads every row
     const int ncol = d->n_levels * d->n_features;
@@ -1450,17 +1403,9 @@ extern "C" int anr_hashgrid_bwd_rows(const anr_hashgrid_desc* d, const float* x,
     ANR_CHECK_LAUNCH("anr_hashgrid_bwd_rows(zero)");
     return anr_hashgrid_bwd(d, x, x_stride, M, dout, dout_dtype, dout_stride, dtable, stream);
   }
-  const dim3 grid(static_cast<unsigned>(ceil_div(ceil_div(M, K), 4))), block(256);
-  if (dout_dtype == ANR_F16)
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, __half, 3, 32, false, HASH_BS, true>), grid,
-                       block, 0, as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const __half*>(dout), dout_stride, dtable, 2, nullptr,
-                       nullptr, row_nz);
-  else
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<3, float, 3, 32, false, HASH_BS, true>), grid,
-                       block, 0, as_stream(stream), G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const float*>(dout), dout_stride, dtable, 2, nullptr,
-                       nullptr, row_nz);
+  launch_bwd_v2<3, 3, 32, false, HASH_BS, true>(G, d, x, x_stride, M, K, dout, dout_dtype,
+                                                dout_stride, dtable, as_stream(stream), nullptr,
+                                                nullptr, row_nz);
   ANR_CHECK_LAUNCH("anr_hashgrid_bwd_rows");
   return ANR_OK;
 }

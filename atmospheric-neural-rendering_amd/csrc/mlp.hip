@@ -409,11 +409,8 @@ int mlp_fused_try(const anr_mlp_desc* d, int32_t precision, bool bwd, const void
                   float* slab = nullptr, int64_t slab_floats = 0, float loss_scale = 0.0f);
 bool mlp_fused_has(const anr_mlp_desc* d);
 
-// ANR_MLP_GENERIC=1 (or anr_mlp_force_generic) forces the generic kernels.
-static int g_force_generic = [] {
-  const char* e = getenv("ANR_MLP_GENERIC");
-  return (e && e[0] == '1') ? 1 : 0;
-}();
+// anr_mlp_force_generic forces the generic kernels.
+static int g_force_generic = 0;
 static bool force_generic() { return g_force_generic != 0; }
 
 }  // namespace anr

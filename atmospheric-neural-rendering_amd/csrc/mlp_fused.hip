@@ -613,33 +613,16 @@ static int launch(bool bwd, const Args& a, hipStream_t st) {
   }
   if (lds > 160 * 1024) return 1;  // does not fit: caller falls back to the generic kernel
   const int64_t tiles = (a.M + 15) / 16;
-  int64_t blocks = (tiles + waves - 1) / waves;
+  const int64_t work = (tiles + waves - 1) / waves;
   (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   // bwd: one resident wave per slot, each folding many tiles into its register dW (so
-  // the flush atomics stay few); size the grid to what is co-resident (once per kernel)
-  static int per_cu[2] = {0, 0};
-  int& pc = per_cu[bwd ? 1 : 0];
-  if (pc == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * waves, lds) != hipSuccess || nb < 1)
-      nb = 1;
-    pc = nb;
-  }
-  const int64_t cap = bwd ? 256LL * pc : 2048;
-  if (blocks > cap) blocks = cap;
-  if (bwd) {
-    // Minimum tiles per wave (profiling override ANR_MLP_BWD_MIN_TILES). On the per-ray
-    // surface network (8192 rows) 8 tiles per wave (64 waves, 64 flush adds per weight
-    // instead of 512) measured 0.104 ms against 0.057 ms with one tile per wave: the
-    // serial tile walk costs more than the contended flush saves, so the default is 1.
-    static const int64_t min_tiles = [] {
-      const char* e = getenv("ANR_MLP_BWD_MIN_TILES");
-      const long long v = e ? atoll(e) : 0;
-      return v > 0 ? static_cast<int64_t>(v) : static_cast<int64_t>(1);
-    }();
-    const int64_t by_tiles = (tiles + waves * min_tiles - 1) / (waves * min_tiles);
-    if (blocks > by_tiles) blocks = by_tiles > 0 ? by_tiles : 1;
-  }
+  // the flush atomics stay few); size the grid to what is co-resident. A wave takes as few
+  // tiles as that allows: on the per-ray surface network (8192 rows) 8 tiles per wave (64
+  // waves, 64 flush adds per weight instead of 512) measured 0.104 ms against 0.057 ms with
+  // one tile per wave: the serial tile walk costs more than the contended flush saves.
+  // fwd: at most 2,048 blocks, grid-stride.
+  const int64_t blocks = bwd ? persistent_blocks(work, blocks_per_cu(fn, 64 * waves, lds))
+                             : (work < 2048 ? work : 2048);
   if (bwd) {
     Args b = a;
     if (a.slab && blocks * waves * static_cast<int64_t>(S::n_params) > a.slab_floats)

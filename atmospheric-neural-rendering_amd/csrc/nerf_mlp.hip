@@ -548,14 +548,17 @@ __global__ void __launch_bounds__(256) dw_reduce_kernel(const float* __restrict_
 
 // M in chunks whose A operands stay below 2^31 bytes (32-bit buffer offsets); a
 // persistent grid walks each chunk's row tiles (64 x 64 wave tiles at two waves per SIMD,
-// 1,024 blocks; ANR_NERF_BIG=1: 128 x 128 at one wave per SIMD, 256 blocks, for P = 256)
-// Operand stages of the k loop: three (loads two k-steps ahead) unless ANR_NERF_STAGES=2
-// (A/B hook). Against two stages on one box: the NeRF step 41.5 -> 40.6 ms, the narrow
-// launches gaining most (256 x 260 forward 1.51 -> 1.40 ms: fc9's 4 density columns stream
-// A with little MFMA work per load); the 256 x 256 layers, which pay two padding steps per
-// tile, are unchanged (profiles/r05_nerf_stages_ab.log).
-static int g_nt_stages = getenv("ANR_NERF_STAGES") ? atoi(getenv("ANR_NERF_STAGES")) : 3;
-template <int WR, int WC, int TI, int TJ, int WPE>
+// 1,024 blocks).
+// Operand stages of the k loop: three (loads two k-steps ahead). Against two stages on one
+// box: the NeRF step 41.5 -> 40.6 ms, the narrow launches gaining most (256 x 260 forward
+// 1.51 -> 1.40 ms: fc9's 4 density columns stream A with little MFMA work per load); the
+// 256 x 256 layers, which pay two padding steps per tile, are unchanged
+// (profiles/r05_nerf_stages_ab.log).
+// P = 256 layers on 128 x 128 wave tiles (256 AGPR accumulators, one wave per SIMD, 256
+// blocks; the compiler spills 24 VGPRs of the epilogue's temporaries to scratch) measured
+// 3-6 % faster as kernels alone (profiles/r05_nerf_big_tiles.log) and the same as a NeRF
+// step (43.22 vs 43.17 ms), so the spill-free 64 x 64 form is the only one launched.
+template <int WR, int WC, int TI, int TJ>
 static void launch_cfg(const NtArgs& a, int64_t blocks_cap, hipStream_t st) {
   const int64_t rows = 16LL * TI * WR;
   const unsigned gy = static_cast<unsigned>(ceil_div(a.P, 16LL * TJ * WC));
@@ -563,17 +566,9 @@ static void launch_cfg(const NtArgs& a, int64_t blocks_cap, hipStream_t st) {
   const int64_t cap = ceil_div(blocks_cap, gy);
   gx = gx < cap ? gx : cap;
   const dim3 grid(static_cast<unsigned>(gx), gy);
-  if (g_nt_stages != 2 && WPE == 2)
-    nt_kernel<WR, WC, TI, TJ, WPE, 3><<<grid, 256, 0, st>>>(a);
-  else
-    nt_kernel<WR, WC, TI, TJ, WPE, 2><<<grid, 256, 0, st>>>(a);
+  nt_kernel<WR, WC, TI, TJ, 2, 3><<<grid, 256, 0, st>>>(a);
 }
 
-// ANR_NERF_BIG=1: P = 256 layers on 128 x 128 wave tiles, 256 AGPR accumulators, one wave
-// per SIMD (the compiler spills 24 VGPRs of the epilogue's temporaries to scratch). The
-// kernels alone measured 3-6 % faster (profiles/r05_nerf_big_tiles.log), the NeRF step
-// the same (43.22 vs 43.17 ms), so the spill-free 64 x 64 form stays the default.
-static int g_nt_big = getenv("ANR_NERF_BIG") ? atoi(getenv("ANR_NERF_BIG")) : 0;
 static void launch_nt(NtArgs a, hipStream_t st) {
   const int64_t ld = a.lda1 > a.lda2 ? a.lda1 : a.lda2;
   const int64_t chunk = ((0x7fffffffLL / (ld * 4)) / 256) * 256;
@@ -587,12 +582,8 @@ static void launch_nt(NtArgs a, hipStream_t st) {
     b.c2 = a.c2 + r0 * a.ldc2;
     if (a.bits) b.bits = a.bits + r0 * a.wpr;
     if (a.mbits) b.mbits = a.mbits + r0 * a.wpr;
-    if (g_nt_big && a.P == 256) {
-      launch_cfg<2, 2, 8, 8, 1>(b, 256, st);
-      continue;
-    }
     if (a.P <= 128) {
-      launch_cfg<2, 2, 4, 4, 2>(b, 1024, st);
+      launch_cfg<2, 2, 4, 4>(b, 1024, st);
       continue;
     }
     // the first 256 columns with four 64-wide column waves per block; columns past 256
@@ -602,7 +593,7 @@ static void launch_nt(NtArgs a, hipStream_t st) {
     NtArgs m = b;
     m.P = a.P < 256 ? a.P : 256;
     m.p1 = a.p1 < m.P ? a.p1 : m.P;
-    launch_cfg<1, 4, 4, 4, 2>(m, 1024, st);
+    launch_cfg<1, 4, 4, 4>(m, 1024, st);
     if (a.P > 256) {
       NtArgs t = b;
       t.P = a.P - 256;
@@ -621,7 +612,7 @@ static void launch_nt(NtArgs a, hipStream_t st) {
       }
       if (b.bits) t.bits = b.bits + 4;
       if (t.mbits) t.mbits = b.mbits + 4;
-      launch_cfg<2, 2, 4, 4, 2>(t, 1024, st);
+      launch_cfg<2, 2, 4, 4>(t, 1024, st);
     }
   }
 }

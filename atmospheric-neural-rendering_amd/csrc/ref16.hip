@@ -671,17 +671,12 @@ __global__ void __launch_bounds__(256) quantize_kernel(float* __restrict__ g, in
 }
 
 // Rays per wavefront: 2 from 8,192 rays up, 1 below (fewer rays leave SIMDs idle, and
-// then one ray per wave's extra waves beat the shared scans); ANR_REF16_R = 1 / 2 / 4 / 8
-// or anr_composite_ref16_set_rays overrides (r04 sweep in DESIGN.md §10). Halved until
-// the band-sum lanes R * C fit the wave.
+// then one ray per wave's extra waves beat the shared scans); anr_composite_ref16_set_rays
+// (1 / 2 / 4 / 8) overrides (r04 sweep in DESIGN.md §10). Halved until the band-sum lanes
+// R * C fit the wave.
 static int g_rays = 0;
 static int rays_per_wave(int C, int64_t B) {
-  static const int env = [] {
-    const char* s = getenv("ANR_REF16_R");
-    const int v = s ? atoi(s) : 0;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0;
-  }();
-  int R = g_rays ? g_rays : (env ? env : (B >= 8192 ? 2 : 1));
+  int R = g_rays ? g_rays : (B >= 8192 ? 2 : 1);
   while (R > 1 && R * C > 64) R /= 2;
   return R;
 }

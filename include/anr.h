@@ -191,7 +191,7 @@ int anr_hashgrid_fwd_runs(const anr_hashgrid_desc* d, const float* x, int64_t x_
                           int64_t out_stride, anr_stream_t stream);
 
 /* Kernel generation (test / A-B hook; process-wide; returns the previous mode, or
- * ANR_E_INVALID for an unknown mode; also ANR_HASHGRID_MODE): 0 = default (forward v6
+ * ANR_E_INVALID for an unknown mode): 0 = default (forward v6
  * branch-free walker -- v1 above 16 levels or past 32-bit buffer offsets -- backward v2
  * four-lanes-per-level), 1 = v1 both, 6 = forward v1 + backward v2 (the r01 default),
  * 7 = mode 0 with the backward's run-time-stride instantiation. */
@@ -596,7 +596,7 @@ int anr_loss_fwd_bwd(int32_t loss_type, const void* color_map, int32_t pred_dtyp
  * Replaces render_with_surface (graphics_utils.py:52-77) at instant_ngp.py:187-192 in that
  * mode. */
 /* Rays per wavefront of the two composite kernels: 1, 2, 4 or 8, or 0 for the default
- * (2 from 8,192 rays up, else 1; or ANR_REF16_R); halved while R * C > 64. Outputs do
+ * (2 from 8,192 rays up, else 1); halved while R * C > 64. Outputs do
  * not depend on it. */
 int anr_composite_ref16_set_rays(int32_t rays_per_wave);
 int anr_composite_ref16_fwd(const float* z, float z_scale, const void* color,

@@ -369,16 +369,13 @@ def mlp_path(request):
     _lib.load().anr_mlp_force_generic(prev)
 
 
-@pytest.mark.parametrize("n_in,n_out,width,n_hidden,out_relu", MLP_CASES)
-@pytest.mark.parametrize("half", [False, True])
-def test_mlp_fwd_bwd(dev, mlp_path, n_in, n_out, width, n_hidden, out_relu, half):
+def _mlp_fwd_bwd(dev, n_in, n_out, width, n_hidden, out_relu, half, M):
     from atmonr_amd import _lib
 
     d = _lib.mlp_desc(n_in, n_out, width, n_hidden, out_relu)
     nparam = _lib.load().anr_mlp_n_params(ctypes.byref(d))
     gen = torch.Generator().manual_seed(width + n_in)
     params = torch.randn(nparam, generator=gen) * (1.0 / width) ** 0.5
-    M = 1001  # not a multiple of the 16-row tile
     x = torch.randn(M, n_in, generator=gen)
     dt = torch.float16 if half else torch.float32
     prec = _lib.F16 if half else _lib.F32
@@ -403,6 +400,24 @@ def test_mlp_fwd_bwd(dev, mlp_path, n_in, n_out, width, n_hidden, out_relu, half
               _lib.F32, n_in, dparams.data_ptr(), s)
     close(din, xr.grad, rel=rel * 2, atol=1e-8)
     close(dparams, pr.grad, rel=rel * 2, atol=1e-8)
+
+
+@pytest.mark.parametrize("n_in,n_out,width,n_hidden,out_relu", MLP_CASES)
+@pytest.mark.parametrize("half", [False, True])
+def test_mlp_fwd_bwd(dev, mlp_path, n_in, n_out, width, n_hidden, out_relu, half):
+    # 1001 rows: not a multiple of the 16-row tile
+    _mlp_fwd_bwd(dev, n_in, n_out, width, n_hidden, out_relu, half, 1001)
+
+
+@pytest.mark.parametrize("n_in,n_out,width,n_hidden,out_relu", [MLP_CASES[1], MLP_CASES[2]])
+@pytest.mark.parametrize("half", [False, True])
+@pytest.mark.parametrize("M", [1, 131089])
+def test_mlp_fwd_bwd_grid_clamps(dev, n_in, n_out, width, n_hidden, out_relu, half, M):
+    """The specialised kernels' grid clamps, same oracle and tolerances as test_mlp_fwd_bwd.
+    One row: the smallest grid. 131,089 rows = 16 * 4 * 256 * 8 + 17: a CU holds at most 8
+    of these 4-wave blocks, so the 16-row tiles outnumber the wavefronts of the backward's
+    largest possible grid (and the forward's 2,048 blocks), with a ragged last tile."""
+    _mlp_fwd_bwd(dev, n_in, n_out, width, n_hidden, out_relu, half, M)
 
 
 @pytest.mark.parametrize("n_in,n_out,width,n_hidden,out_relu", MLP_CASES)
@@ -865,11 +880,12 @@ def test_ingp_field_unsupported_and_empty(dev):
 
 
 @pytest.mark.parametrize("mma", ["f16", "bf16"])
-@pytest.mark.parametrize("width,nhd,M", [(64, 2, 2654208), (64, 2, 77), (32, 1, 1000)])
+@pytest.mark.parametrize("width,nhd,M", [(64, 2, 2654208), (64, 2, 77), (32, 1, 1000), (32, 1, 1)])
 def test_ingp_field_density_equals_field_sigma(dev, width, nhd, M, mma):
     """anr_ingp_field_density (the pos MLP only: extract / occupancy) returns exactly the
-    full field forward's sigma, at the extract batch (32,768 columns x 81 altitudes) and
-    ragged sizes."""
+    full field forward's sigma, at the extract batch (32,768 columns x 81 altitudes),
+    ragged sizes and a single row (the smallest grid; with this seed its density is
+    positive at width 32, so the last assertion holds there)."""
     from atmonr_amd import _lib
 
     nb = 4
@@ -998,7 +1014,7 @@ def _field_torch_f32(enc_h, dirs, n_per_ray, pp, pd, width, nhd, nb, h):
     P0 = h(pp[: 32 * width]).view(width, 32)
     P1 = h(pp[32 * width:]).view(16, width)
     po = h(torch.relu(h(enc_h.float()) @ P0.T)) @ P1.T
-    d = dirs.repeat_interleave(n_per_ray, 0) * 2 - 1
+    d = dirs.repeat_interleave(n_per_ray, 0)[: po.shape[0]] * 2 - 1  # a ragged last ray
     c1 = 0.48860251190291987
     sh = torch.stack([torch.full_like(d[:, 0], 0.28209479177387814), -c1 * d[:, 1],
                       c1 * d[:, 2], -c1 * d[:, 0]], 1)
@@ -1013,20 +1029,19 @@ def _field_torch_f32(enc_h, dirs, n_per_ray, pp, pd, width, nhd, nb, h):
     return torch.relu(po[:, 0]), torch.relu(x[:, :nb])
 
 
-@pytest.mark.timeout(300)
-@pytest.mark.parametrize("mma", ["f16", "bf16"])
-def test_ingp_field_bench_size(dev, mma):
-    """Fused field at the bench size (8192 rays x 1024 samples, width 64, 2 dir layers)
-    against the same network in torch f32 on the device with the kernel's 16-bit
-    roundings (autograd for the gradients), plus 2,048 spot rows against the f64 CPU
-    oracle. Tolerances (of the largest value): sigma / color 2e-2 (f16) / 4e-2 (bf16) on
-    every row; d_enc within 5e-2 on >= 99.9 % of rows (a ReLU input within rounding of 0
-    can switch sides between two evaluation orders, changing that row's gradient path);
-    parameter gradients (sums over 8.4 M rows) 2e-2 / 5e-2 relative L2."""
+def _field_vs_torch_f32(dev, mma, R, n_per_ray, extra=0):
+    """Fused field forward and backward (width 64, 2 dir layers) on R rays of n_per_ray
+    samples plus `extra` rows of one more ray, against the same network in torch f32 on the
+    device with the kernel's 16-bit roundings (autograd for the gradients), plus up to two
+    rays of spot rows against the f64 CPU oracle. Tolerances (of the largest value): sigma /
+    color 2e-2 (f16) / 4e-2 (bf16) on every row; d_enc within 5e-2 on >= 99.9 % of rows (a
+    ReLU input within rounding of 0 can switch sides between two evaluation orders, changing
+    that row's gradient path); parameter gradients (sums over the rows) 2e-2 / 5e-2 relative
+    L2."""
     from atmonr_amd import _lib
 
-    width, nhd, nb, R, n_per_ray = 64, 2, 4, 8192, 1024
-    M = R * n_per_ray
+    width, nhd, nb = 64, 2, 4
+    M = R * n_per_ray + extra
     bf = mma == "bf16"
     code = _lib.BF16 if bf else _lib.F16
     rtype = torch.bfloat16 if bf else torch.float16
@@ -1039,7 +1054,8 @@ def test_ingp_field_bench_size(dev, mma):
     pp = torch.randn(lib.anr_mlp_n_params(pb), device=dev, generator=g) * (2.0 / 32) ** 0.5
     pd = torch.randn(lib.anr_mlp_n_params(db), device=dev, generator=g) * (2.0 / width) ** 0.5
     enc = (torch.rand(M, 32, device=dev, generator=g) * 2 - 1).half()
-    dirs = torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=1) * 0.5 + 0.5
+    n_rays = R + (1 if extra else 0)
+    dirs = torch.nn.functional.normalize(torch.randn(n_rays, 3, device=dev, generator=g), dim=1) * 0.5 + 0.5
     s = _lib.stream(dev)
     packed = torch.empty(lib.anr_ingp_field_packed_size(pb, db), device=dev, dtype=torch.float16)
     _lib.call("anr_ingp_field_pack", pb, db, code, pp.data_ptr(), pd.data_ptr(),
@@ -1069,7 +1085,7 @@ def test_ingp_field_bench_size(dev, mma):
     assert ok >= 0.999, ok
     for a, b in ((g_pos, tp.grad), (g_dir, td.grad)):
         assert ((a - b).norm() / b.norm()).item() <= rg
-    # 2,048 spot rows against the f64 CPU oracle (whole rays, so n_per_ray stays intact)
+    # spot rows against the f64 CPU oracle (two whole rays, so n_per_ray stays intact)
     rays = torch.randperm(R, generator=torch.Generator().manual_seed(3))[:2]
     rows = (rays[:, None] * n_per_ray + torch.arange(n_per_ray)[None]).reshape(-1).to(dev)
     half = "bf16" if bf else True
@@ -1078,6 +1094,26 @@ def test_ingp_field_bench_size(dev, mma):
                                   nb, half)
     close(sigma[rows], rs64, rel=rf, atol=1e-5)
     close(color[rows], rc64, rel=rf, atol=1e-5)
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("mma", ["f16", "bf16"])
+def test_ingp_field_bench_size(dev, mma):
+    """Fused field at the bench size (8192 rays x 1024 samples): _field_vs_torch_f32, with
+    parameter gradients that are sums over 8.4 M rows and 2,048 spot rows."""
+    _field_vs_torch_f32(dev, mma, 8192, 1024)
+
+
+@pytest.mark.parametrize("mma", ["f16", "bf16"])
+@pytest.mark.parametrize("R,n_per_ray,extra", [(1, 1, 0), (256, 1024, 33)])
+def test_ingp_field_grid_clamps(dev, mma, R, n_per_ray, extra):
+    """The two clamps of the field's persistent grids, same oracle and tolerances as the
+    bench size. One row: the smallest grid (one block, three idle wavefronts). 262,177 rows
+    = 32 * 4 * 256 * 8 + 33: a CU holds at most 8 of these 4-wave blocks, so the forward's
+    16-row tiles and the backward's 32-row tiles both outnumber the wavefronts of the
+    largest possible grid (every wavefront walks more than one tile), and the last tile is
+    ragged."""
+    _field_vs_torch_f32(dev, mma, R, n_per_ray, extra)
 
 
 @pytest.mark.parametrize("tdt", ["f16", "f32"])
@@ -1287,6 +1323,20 @@ def test_ingp_field_bwd_zero_gradient_tiles(dev, ref):
         assert (d_all[~zero] - d_live).abs().max().item() <= 1e-2 * d_live.abs().max().item()
         tol = 1e-2
     for a_, b_ in ((gp_all, gp_live), (gd_all, gd_live)):
+        assert (a_ - b_).abs().max().item() <= tol * b_.abs().max().item()
+    # the smallest grid: one live ray alone (one block, two of its four wavefronts idle)
+    # gives that ray's rows of the launches above, and with a launch over the other live
+    # rays it adds up to their parameter gradients, to the same tolerances
+    one, rest = live[3], live[:3] + live[4:]
+    d_one, gp_one, gd_one = run([one])
+    _, gp_rest, gd_rest = run(rest)
+    d_ray = d_live.view(len(live), n_per_ray, 32)[3]
+    if ref:
+        assert torch.equal(d_one, d_ray)
+    else:
+        assert (d_one - d_ray).abs().max().item() <= 1e-2 * d_live.abs().max().item()
+    assert (d_one != 0).any()
+    for a_, b_ in ((gp_one + gp_rest, gp_live), (gd_one + gd_rest, gd_live)):
         assert (a_ - b_).abs().max().item() <= tol * b_.abs().max().item()
 
 
@@ -1545,13 +1595,13 @@ def test_hashgrid_bwd_rows_outside_walker_zeroes_clear_rows(dev):
 
 @pytest.mark.parametrize("mma", ["f16", "bf16"])
 @pytest.mark.parametrize("width,nhd", [(64, 2), (64, 1), (32, 2)])
-@pytest.mark.parametrize("R,n_per_ray", [(37, 64), (5, 1024), (8192, 1024)])
+@pytest.mark.parametrize("R,n_per_ray", [(37, 64), (5, 1024), (8192, 1024), (1, 64)])
 def test_hash_field_fwd_equals_two_kernels(dev, mma, width, nhd, R, n_per_ray):
     """anr_ingp_hash_field_fwd (r06: hash grid + field forward in one kernel) against
     anr_hashgrid_fwd_planes followed by anr_ingp_field_fwd on the planes: the planes it
     writes and sigma / colour are bit-identical, on ray-like coordinates (16 levels, T =
-    2^19, f16 table), for every supported field shape, f16 and bf16 MFMA, a ragged ray count
-    and the bench size (8,192 rays x 1,024 samples). Shapes outside its set (samples per ray
+    2^19, f16 table), for every supported field shape, f16 and bf16 MFMA, a ragged ray count,
+    the bench size (8,192 rays x 1,024 samples) and a single 64-sample ray. Shapes outside its set (samples per ray
     not a multiple of 64) are refused with ANR_E_UNSUPPORTED."""
     from atmonr_amd import _lib
 

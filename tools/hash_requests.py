@@ -28,7 +28,7 @@ U32 = 0xFFFFFFFF
 
 def bwd_chunk(M: int) -> int:
     """pick_chunk_v2 (csrc/hashgrid.hip): samples per wave of the v2 backward, asked of
-    the library itself (anr_hashgrid_bwd_chunk, ANR_HASH_KB included)."""
+    the library itself (anr_hashgrid_bwd_chunk)."""
     from atmonr_amd import _lib
 
     return int(_lib.load().anr_hashgrid_bwd_chunk(int(M)))

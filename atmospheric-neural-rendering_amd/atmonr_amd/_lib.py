@@ -311,6 +311,16 @@ _SIGNATURES = {
         [_P, c_float, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32,
          _P, _P],
     ),
+    "anr_composite_ref16_fwd_park": (
+        c_int32,
+        [_P, c_float, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P, _P,
+         _P, _P, _P, _P],
+    ),
+    "anr_composite_ref16_bwd_parked": (
+        c_int32,
+        [_P, c_float, _P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32,
+         _P, _P, _P, _P],
+    ),
     "anr_loss_ref16_fwd_bwd": (
         c_int32, [c_int32, _P, c_int32, _P, _P, c_int64, c_float, _P, _P, _P, _P]),
     "anr_grad_quantize_f16": (c_int32, [_P, c_int64, c_float, _P]),

@@ -82,7 +82,8 @@ class _CompositeRef16Fn(torch.autograd.Function):
     """render_with_surface with the reference's f16 numerics (anr_composite_ref16_*)."""
 
     @staticmethod
-    def forward(ctx, z, color, sigma, color_surf, z_scale: float, zero_rays, want16: bool):
+    def forward(ctx, z, color, sigma, color_surf, z_scale: float, zero_rays, want16: bool,
+                need_alpha: bool, park: bool):
         B, N, C = color.shape
         if sigma.shape[2] != 1:
             raise ANRError("reference-numerics composite: one density channel (B, N, 1)")
@@ -95,23 +96,35 @@ class _CompositeRef16Fn(torch.autograd.Function):
         atmo = torch.empty(B, C, device=dev, dtype=f16)
         surf = torch.empty(B, C, device=dev, dtype=f16) if cs is not None else None
         weights = torch.empty(B, N, 1, device=dev, dtype=f16)
-        alpha = torch.empty(B, N, 1, device=dev, dtype=f16)
+        alpha = torch.empty(B, N, 1, device=dev, dtype=f16) if need_alpha else None
         # f16 inputs hold the f16 values already: no copies are written, the inputs themselves
         # are saved for the backward and returned as the f16 colour / density results
         copies = want16 and color.dtype != f16
         c16 = torch.empty(B, N, C, device=dev, dtype=f16) if copies else None
         s16 = torch.empty(B, N, 1, device=dev, dtype=f16) if copies else None
-        call("anr_composite_ref16_fwd", ptr(zc), float(z_scale), ptr(color), ptr(sigma), ptr(cs),
-             dtype_code(color.dtype), B, N, C, ptr(cm), ptr(atmo), ptr(surf), ptr(weights),
-             ptr(alpha), ptr(c16), ptr(s16), _lib.stream(dev), tag="composite_fwd")
+        args = (ptr(zc), float(z_scale), ptr(color), ptr(sigma), ptr(cs),
+                dtype_code(color.dtype), B, N, C, ptr(cm), ptr(atmo), ptr(surf), ptr(weights),
+                ptr(alpha), ptr(c16), ptr(s16))
+        if park:
+            # a backward will follow on these same tensors: the kernel also leaves it T_i and
+            # exp(-sigma_i delta_i) (one 4-byte pair per sample) and, per ray, the surface
+            # product and the alpha-is-1 flag, so the backward does not replay the forward
+            pk = torch.empty(B, N, device=dev, dtype=torch.int32)
+            rpk = torch.empty(B, device=dev, dtype=torch.int32)
+            call("anr_composite_ref16_fwd_park", *args, ptr(pk), ptr(rpk), _lib.stream(dev),
+                 tag="composite_fwd")
+        else:
+            pk = rpk = None
+            call("anr_composite_ref16_fwd", *args, _lib.stream(dev), tag="composite_fwd")
         # the backward reads the inputs as f16 values either way: with the f16 copies at
         # hand it reads those (half the bytes of f32 inputs) and still returns gradients in
         # the inputs' dtype
         ctx.out_dtype = color.dtype
+        ctx.parked = park
         if copies:
-            ctx.save_for_backward(zc, c16, s16, cs)
+            ctx.save_for_backward(zc, c16, s16, cs, pk, rpk)
         else:
-            ctx.save_for_backward(zc, color, sigma, cs)
+            ctx.save_for_backward(zc, color, sigma, cs, pk, rpk)
             if want16:
                 c16, s16 = color.detach(), sigma.detach()
         ctx.set_materialize_grads(False)
@@ -125,7 +138,7 @@ class _CompositeRef16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_cm, *unused):
-        zc, color, sigma, cs = ctx.saved_tensors
+        zc, color, sigma, cs, pk, rpk = ctx.saved_tensors
         if any(g is not None for g in unused):
             raise ANRError("reference-numerics composite: gradients flow through color_map "
                            "only (as in the reference's loss)")
@@ -141,14 +154,20 @@ class _CompositeRef16Fn(torch.autograd.Function):
                 if cs is not None and ctx.needs_input_grad[3] else None)
         if cs is not None and cs.dtype != color.dtype:
             cs = cs.to(color.dtype)
-        call("anr_composite_ref16_bwd", ptr(zc), ctx.z_scale, ptr(color), ptr(sigma), ptr(cs),
-             dtype_code(color.dtype), B, N, C, ptr(g_cm), ptr(d_color), ptr(d_sigma), ptr(d_cs),
-             dtype_code(od), ptr(ctx.zero_rays), _lib.stream(dev), tag="composite_bwd")
-        return None, d_color, d_sigma, d_cs, None, None, None
+        args = (ptr(zc), ctx.z_scale, ptr(color), ptr(sigma), ptr(cs), dtype_code(color.dtype),
+                B, N, C, ptr(g_cm), ptr(d_color), ptr(d_sigma), ptr(d_cs), dtype_code(od),
+                ptr(ctx.zero_rays))
+        if pk is not None:
+            call("anr_composite_ref16_bwd_parked", *args, ptr(pk), ptr(rpk), _lib.stream(dev),
+                 tag="composite_bwd")
+        else:
+            call("anr_composite_ref16_bwd", *args, _lib.stream(dev), tag="composite_bwd")
+        return None, d_color, d_sigma, d_cs, None, None, None, None, None
 
 
 def render_with_surface_ref16(z_vals, color, sigma, color_surf, z_scale: float = 1.0,
-                              zero_rays: torch.Tensor | None = None, inputs_f16: bool = False):
+                              zero_rays: torch.Tensor | None = None, inputs_f16: bool = False,
+                              need_alpha: bool = True):
     """graphics_utils.py:52-77 with the reference's Instant-NGP numerics: z cast to f16
     (after the f32 ``z_vals * z_scale``), every op rounded to f16, torch's CUDA
     accumulation (f16 cumprod / cumsum, f32 sum / prod), and torch's f16 autograd as the
@@ -160,12 +179,19 @@ def render_with_surface_ref16(z_vals, color, sigma, color_surf, z_scale: float =
     color and sigma rounded to f16 as the kernel reads them (tcnn's f16 outputs, which the
     reference's forward returns), written by the same kernel; f16 color / sigma are returned
     as they are (no copy). f16 inputs also get f16 gradients, and the backward then parks its
-    two scratch values per sample as one 4-byte pair (csrc/ref16.hip)."""
+    two scratch values per sample as one 4-byte pair (csrc/ref16.hip). ``need_alpha=False``:
+    alpha is not written and its slot of the result is None. When a gradient can flow
+    (grad mode on and color, sigma or color_surf requires grad) the forward also parks T,
+    exp(-sigma delta) and the surface product for its backward (4 bytes per sample, held
+    until the backward ran), which then skips its replay of the forward; an inference
+    forward writes no park."""
     _check(z_vals, color, sigma)
     if zero_rays is None:
         zero_rays = torch.zeros(1, dtype=torch.int32, device=color.device)
+    park = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (color, sigma, color_surf))
     return _CompositeRef16Fn.apply(z_vals, color, sigma, color_surf, z_scale, zero_rays,
-                                   bool(inputs_f16))
+                                   bool(inputs_f16), bool(need_alpha), park)
 
 
 def _check(z_vals, color, sigma):

@@ -267,7 +267,7 @@ class InstantNGPPipeline(Pipeline):
             # or (f32 field outputs: ANR_HASH_FIELD=1, ANR_REF_F16_IO=0) copies the kernel writes
             color_map, _, weights, atmo, surf, color, sigma = render_with_surface_ref16(
                 z_vals, color, sigma, color_surf, z_scale=self.scale / 1000,
-                zero_rays=self._zero_rays, inputs_f16=True)
+                zero_rays=self._zero_rays, inputs_f16=True, need_alpha=False)
             if color_map.requires_grad:
                 color_map = _TcnnGradsAtBackwardEnd.apply(color_map, self)
         else:

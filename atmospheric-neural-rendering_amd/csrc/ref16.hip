@@ -192,7 +192,20 @@ __device__ __forceinline__ float add_h(float acc, _Float16 x) {
 }
 constexpr float kNegZero = -0.0f;
 
-template <int R, typename T>
+__device__ __forceinline__ uint32_t f16_bits(float x) {  // x holds an f16 value
+  return __builtin_bit_cast(uint16_t, static_cast<_Float16>(x));
+}
+__device__ __forceinline__ float f16_value(uint32_t bits) {
+  return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(bits)));
+}
+
+// PARK: the forward also leaves what its backward would otherwise recompute from z and
+// sigma (bwd_kernel's pass 1): per sample one 4-byte word, the f16 bits of T_i (low half)
+// and of exp(-sigma_i delta_i) (high half) -- the pair format bwd_kernel's pass 2 reads --
+// and per ray the f16 bits of the surface product h(pr) with bit 16 set where some sample's
+// q2 is 0 (an f16 alpha of 1). Every training step runs this forward and then the backward
+// on the same tensors, so the backward's replay was the same work done twice.
+template <int R, typename T, bool PARK>
 __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, float zs,
                                                  const T* __restrict__ color,
                                                  const T* __restrict__ sigma,
@@ -200,7 +213,8 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
                                                  int C, __half* cmap, __half* atmo_out,
                                                  __half* surf_out, __half* weights,
                                                  __half* alpha_out, __half* color16,
-                                                 __half* sigma16) {
+                                                 __half* sigma16, uint32_t* park,
+                                                 uint32_t* ray_park) {
   __shared__ FwdLds<R> L;
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * R;
   const int nr = B - b0 < R ? static_cast<int>(B - b0) : R;  // rays of this wave
@@ -209,6 +223,7 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
   _Float16 cp = 1.0f;  // lane r < nr: ray r's cumprod output, f16 accumulator (cuda scan)
   float pr = 1.0f;     // lane r < nr: ray r's prod over samples, f32 accumulator
   float acc = 0.0f;    // lane sr < nr: ray sr's band sc sum over samples, f32 accumulator
+  uint32_t zmask = 0;  // PARK: bit r: ray r has an f16 alpha of 1 (uniform)
   SegIn<R, true, true> nxt;
   nxt.fetch(z, sigma, color, b0, nr, 0, N, C, lane);
   for (int s0 = 0; s0 < N; s0 += kSeg) {
@@ -216,8 +231,11 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
     const int nv = (n + 7) & ~7;
     const SegIn<R, true, true> cur = nxt;
     if (s0 + kSeg < N) nxt.fetch(z, sigma, color, b0, nr, s0 + kSeg, N, C, lane);
+    uint32_t eb[R];  // PARK: the bits of exp(-sigma * delta), stored with T_i after the scan
 #pragma unroll
     for (int r = 0; r < R; ++r) {
+      bool zr = false;
+      eb[r] = 0;
       if (r < nr && lane < n) {
         const int64_t b = b0 + r;
         const float sg = in16<T>(cur.sg[r]);
@@ -225,9 +243,14 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
         const Sample sm = sample(sg, delta_z(cur.zm[r], cur.z0[r], cur.zp[r], zs, s0 + lane, N));
         L.q2[r][lane] = static_cast<_Float16>(sm.q2);
         L.alpha[r][lane] = static_cast<_Float16>(sm.alpha);
+        if (PARK) {
+          eb[r] = f16_bits(sm.e) << 16;
+          zr = sm.q2 == 0.0f;
+        }
       } else if (lane < nv) {
         L.q2[r][lane] = static_cast<_Float16>(1.0f);
       }
+      if (PARK && __any(zr)) zmask |= 1u << r;
     }
     wave_sync();
     if (lane < nr) {
@@ -249,7 +272,9 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
       if (r < nr && lane < n) {
         const int64_t i = (b0 + r) * N + s0 + lane;
         const float al = static_cast<float>(L.alpha[r][lane]);
-        const float w = h(al * static_cast<float>(L.T[r][lane]));   // alpha * T    (:43-46)
+        const _Float16 Ti = L.T[r][lane];
+        const float w = h(al * static_cast<float>(Ti));             // alpha * T    (:43-46)
+        if (PARK) park[i] = __builtin_bit_cast(uint16_t, Ti) | eb[r];
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c) {
           if (c >= C) break;
@@ -283,6 +308,7 @@ __global__ void __launch_bounds__(64) fwd_kernel(const float* __restrict__ z, fl
     if (atmo_out) atmo_out[b * C + c] = __float2half_rn(atmo);
     if (surf_out && cs) surf_out[b * C + c] = __float2half_rn(surf);
   }
+  if (PARK && lane < nr) ray_park[b0 + lane] = f16_bits(h(pr)) | (((zmask >> lane) & 1u) << 16);
 }
 
 // Autograd of fwd_kernel for dL/dcolor_map (oracle/ref_f16.py render_bwd). d_sigma
@@ -303,14 +329,19 @@ struct __attribute__((aligned(16))) BwdLds {
   float pr[R];            // the surface product per ray (f16 value)
 };
 
-template <int R, typename T, typename G>
+// PARKED: the forward left T_i, exp(-sigma_i delta_i), the surface product and the
+// alpha-is-1 flag (fwd_kernel PARK; pk / ray_pk). There is no pass 1 then, sigma is never
+// read, and d_color / d_sigma hold gradients only: pass 2 reads the pairs from pk.
+template <int R, typename T, typename G, bool PARKED>
 __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, float zs,
                                                  const T* __restrict__ color,
                                                  const T* __restrict__ sigma,
                                                  const T* __restrict__ cs, int64_t B, int N,
                                                  int C, const __half* __restrict__ g_cm,
                                                  G* d_color, G* d_sigma, G* d_cs,
-                                                 int* zero_rays) {
+                                                 int* zero_rays,
+                                                 const uint32_t* __restrict__ pk,
+                                                 const uint32_t* __restrict__ ray_pk) {
   __shared__ BwdLds<R> L;
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * R;
   const int nr = B - b0 < R ? static_cast<int>(B - b0) : R;
@@ -346,8 +377,8 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
   float pr = 1.0f;
   uint32_t zmask = 0;  // bit r: ray r has an f16 alpha of 1 (uniform)
   SegIn<R, false, true> nxt;
-  nxt.fetch(z, sigma, color, b0, nr, 0, N, C, lane);
-  for (int s0 = 0; s0 < N; s0 += kSeg) {
+  if (!PARKED) nxt.fetch(z, sigma, color, b0, nr, 0, N, C, lane);
+  for (int s0 = 0; s0 < (PARKED ? 0 : N); s0 += kSeg) {
     const int n = N - s0 < kSeg ? N - s0 : kSeg;
     const int nv = (n + 7) & ~7;
     const SegIn<R, false, true> cur = nxt;
@@ -400,9 +431,15 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
       }
     wave_sync();
   }
+  float prh = h(pr);  // lane r < nr: ray r's surface product as its f16 value
+  if (PARKED) {
+    const uint32_t rp = lane < nr ? ray_pk[b0 + lane] : 0u;
+    prh = f16_value(rp);
+    zmask = static_cast<uint32_t>(__ballot((rp >> 16) & 1u));
+  }
   // surface term: surf = pr * cs -> dL/dpr (sum over bands), dL/dcs
-  const float prr = h(__shfl(pr, sr < R ? sr : 0));
-  if (lane < nr) L.pr[lane] = h(pr);
+  const float prr = __shfl(prh, sr < R ? sr : 0);
+  if (lane < nr) L.pr[lane] = prh;
   if (cs && sr < nr) {
     if (d_cs) d_cs[(b0 + sr) * C + sc] = static_cast<G>(h(gl * prr));
   }
@@ -437,7 +474,11 @@ __global__ void __launch_bounds__(64) bwd_kernel(const float* __restrict__ z, fl
         z0_[r] = zr[i];
         zm_[r] = i > 0 ? zr[i - 1] : 0.0f;
         zp_[r] = i < N - 1 ? zr[i + 1] : 0.0f;
-        if constexpr (GH) {
+        if constexpr (PARKED) {
+          const uint32_t pv = pk[k];
+          tt_[r] = f16_value(pv);
+          ee_[r] = f16_value(pv >> 16);
+        } else if constexpr (GH) {
           uint32_t pv;
           if (pair) {
             pv = park(b0 + r)[i];
@@ -694,12 +735,13 @@ extern "C" int anr_composite_ref16_set_rays(int32_t rays_per_wave) {
   return ANR_OK;
 }
 
-extern "C" int anr_composite_ref16_fwd(const float* z, float z_scale, const void* color,
-                                       const void* sigma, const void* color_surf,
-                                       int32_t in_dtype, int64_t B, int32_t N, int32_t C,
-                                       void* color_map, void* color_map_atmo,
-                                       void* color_map_surf, void* weights, void* alpha,
-                                       void* color16, void* sigma16, anr_stream_t stream) {
+// Both forward entry points: park == nullptr is anr_composite_ref16_fwd as it always was
+static int composite_ref16_fwd(const float* z, float z_scale, const void* color,
+                               const void* sigma, const void* color_surf, int32_t in_dtype,
+                               int64_t B, int32_t N, int32_t C, void* color_map,
+                               void* color_map_atmo, void* color_map_surf, void* weights,
+                               void* alpha, void* color16, void* sigma16, uint32_t* park,
+                               uint32_t* ray_park, anr_stream_t stream) {
   ANR_CHECK_ARG(z && color && sigma && color_map, "anr_composite_ref16_fwd: null argument");
   ANR_CHECK_ARG(B >= 0 && N >= 1 && C >= 1 && C <= ref16::kMaxC,
                 "anr_composite_ref16_fwd: bad shape B=%lld N=%d C=%d", (long long)B, N, C);
@@ -707,36 +749,67 @@ extern "C" int anr_composite_ref16_fwd(const float* z, float z_scale, const void
   if (B == 0) return ANR_OK;
   ANR_CHECK_ARG(B < (1LL << 31), "anr_composite_ref16_fwd: B=%lld too large", (long long)B);
   const int R = ref16::rays_per_wave(C, B);
-#define ANR_R16F(RR, T)                                                                        \
-  hipLaunchKernelGGL((ref16::fwd_kernel<RR, T>), dim3(static_cast<unsigned>(ceil_div(B, RR))), \
+#define ANR_R16F(RR, T, P)                                                                     \
+  hipLaunchKernelGGL((ref16::fwd_kernel<RR, T, P>),                                            \
+                     dim3(static_cast<unsigned>(ceil_div(B, RR))),                             \
                      dim3(64), 0, as_stream(stream), z, z_scale,                               \
                      static_cast<const T*>(color), static_cast<const T*>(sigma),               \
                      static_cast<const T*>(color_surf), B, N, C,                              \
                      static_cast<__half*>(color_map), static_cast<__half*>(color_map_atmo),  \
                      static_cast<__half*>(color_map_surf), static_cast<__half*>(weights),     \
                      static_cast<__half*>(alpha), static_cast<__half*>(color16),              \
-                     static_cast<__half*>(sigma16))
-#define ANR_R16F_T(T)                                                                         \
+                     static_cast<__half*>(sigma16), park, ray_park)
+#define ANR_R16F_T(T, P)                                                                      \
   switch (R) {                                                                                \
-    case 1: ANR_R16F(1, T); break;                                                            \
-    case 2: ANR_R16F(2, T); break;                                                            \
-    case 4: ANR_R16F(4, T); break;                                                            \
-    default: ANR_R16F(8, T); break;                                                           \
+    case 1: ANR_R16F(1, T, P); break;                                                         \
+    case 2: ANR_R16F(2, T, P); break;                                                         \
+    case 4: ANR_R16F(4, T, P); break;                                                         \
+    default: ANR_R16F(8, T, P); break;                                                        \
   }
-  if (in_dtype == ANR_F16) { ANR_R16F_T(__half) } else { ANR_R16F_T(float) }
+  if (park) {
+    if (in_dtype == ANR_F16) { ANR_R16F_T(__half, true) } else { ANR_R16F_T(float, true) }
+  } else {
+    if (in_dtype == ANR_F16) { ANR_R16F_T(__half, false) } else { ANR_R16F_T(float, false) }
+  }
 #undef ANR_R16F_T
 #undef ANR_R16F
   ANR_CHECK_LAUNCH("anr_composite_ref16_fwd");
   return ANR_OK;
 }
 
-extern "C" int anr_composite_ref16_bwd(const float* z, float z_scale, const void* color,
+extern "C" int anr_composite_ref16_fwd(const float* z, float z_scale, const void* color,
                                        const void* sigma, const void* color_surf,
                                        int32_t in_dtype, int64_t B, int32_t N, int32_t C,
-                                       const void* d_color_map, void* d_color, void* d_sigma,
-                                       void* d_color_surf, int32_t out_dtype, int32_t* zero_rays,
-                                       anr_stream_t stream) {
-  ANR_CHECK_ARG(z && color && sigma && d_color_map && d_color && d_sigma && zero_rays,
+                                       void* color_map, void* color_map_atmo,
+                                       void* color_map_surf, void* weights, void* alpha,
+                                       void* color16, void* sigma16, anr_stream_t stream) {
+  return composite_ref16_fwd(z, z_scale, color, sigma, color_surf, in_dtype, B, N, C, color_map,
+                             color_map_atmo, color_map_surf, weights, alpha, color16, sigma16,
+                             nullptr, nullptr, stream);
+}
+
+extern "C" int anr_composite_ref16_fwd_park(const float* z, float z_scale, const void* color,
+                                            const void* sigma, const void* color_surf,
+                                            int32_t in_dtype, int64_t B, int32_t N, int32_t C,
+                                            void* color_map, void* color_map_atmo,
+                                            void* color_map_surf, void* weights, void* alpha,
+                                            void* color16, void* sigma16, uint32_t* park,
+                                            uint32_t* ray_park, anr_stream_t stream) {
+  ANR_CHECK_ARG(park && ray_park, "anr_composite_ref16_fwd_park: null park");
+  return composite_ref16_fwd(z, z_scale, color, sigma, color_surf, in_dtype, B, N, C, color_map,
+                             color_map_atmo, color_map_surf, weights, alpha, color16, sigma16,
+                             park, ray_park, stream);
+}
+
+// Both backward entry points: park == nullptr is anr_composite_ref16_bwd as it always was
+// (the replay of the forward); with a park sigma is not read and may be null
+static int composite_ref16_bwd(const float* z, float z_scale, const void* color,
+                               const void* sigma, const void* color_surf, int32_t in_dtype,
+                               int64_t B, int32_t N, int32_t C, const void* d_color_map,
+                               void* d_color, void* d_sigma, void* d_color_surf,
+                               int32_t out_dtype, int32_t* zero_rays, const uint32_t* park,
+                               const uint32_t* ray_park, anr_stream_t stream) {
+  ANR_CHECK_ARG(z && color && (sigma || park) && d_color_map && d_color && d_sigma && zero_rays,
                 "anr_composite_ref16_bwd: null argument");
   ANR_CHECK_ARG(B >= 0 && N >= 1 && C >= 1 && C <= ref16::kMaxC,
                 "anr_composite_ref16_bwd: bad shape");
@@ -748,30 +821,62 @@ extern "C" int anr_composite_ref16_bwd(const float* z, float z_scale, const void
   if (B == 0) return ANR_OK;
   ANR_CHECK_ARG(B < (1LL << 31), "anr_composite_ref16_bwd: B=%lld too large", (long long)B);
   const int R = ref16::rays_per_wave(C, B);
-#define ANR_R16B(RR, T, G)                                                                     \
-  hipLaunchKernelGGL((ref16::bwd_kernel<RR, T, G>),                                           \
+#define ANR_R16B(RR, T, G, P)                                                                  \
+  hipLaunchKernelGGL((ref16::bwd_kernel<RR, T, G, P>),                                        \
                      dim3(static_cast<unsigned>(ceil_div(B, RR))), dim3(64), 0,               \
                      as_stream(stream), z, z_scale,                                           \
                      static_cast<const T*>(color), static_cast<const T*>(sigma),               \
                      static_cast<const T*>(color_surf), B, N, C,                              \
                      static_cast<const __half*>(d_color_map), static_cast<G*>(d_color),       \
-                     static_cast<G*>(d_sigma), static_cast<G*>(d_color_surf), zero_rays)
-#define ANR_R16B_TG(T, G)                                                                     \
+                     static_cast<G*>(d_sigma), static_cast<G*>(d_color_surf), zero_rays,      \
+                     park, ray_park)
+#define ANR_R16B_TG(T, G, P)                                                                  \
   switch (R) {                                                                                \
-    case 1: ANR_R16B(1, T, G); break;                                                         \
-    case 2: ANR_R16B(2, T, G); break;                                                         \
-    case 4: ANR_R16B(4, T, G); break;                                                         \
-    default: ANR_R16B(8, T, G); break;                                                        \
+    case 1: ANR_R16B(1, T, G, P); break;                                                      \
+    case 2: ANR_R16B(2, T, G, P); break;                                                      \
+    case 4: ANR_R16B(4, T, G, P); break;                                                      \
+    default: ANR_R16B(8, T, G, P); break;                                                     \
   }
-  if (in_dtype == ANR_F16) {
-    if (out_dtype == ANR_F16) { ANR_R16B_TG(__half, __half) } else { ANR_R16B_TG(__half, float) }
-  } else {
-    if (out_dtype == ANR_F16) { ANR_R16B_TG(float, __half) } else { ANR_R16B_TG(float, float) }
+#define ANR_R16B_P(P)                                                                         \
+  if (in_dtype == ANR_F16) {                                                                  \
+    if (out_dtype == ANR_F16) { ANR_R16B_TG(__half, __half, P) }                              \
+    else { ANR_R16B_TG(__half, float, P) }                                                    \
+  } else {                                                                                    \
+    if (out_dtype == ANR_F16) { ANR_R16B_TG(float, __half, P) }                               \
+    else { ANR_R16B_TG(float, float, P) }                                                     \
   }
+  if (park) { ANR_R16B_P(true) } else { ANR_R16B_P(false) }
+#undef ANR_R16B_P
 #undef ANR_R16B_TG
 #undef ANR_R16B
   ANR_CHECK_LAUNCH("anr_composite_ref16_bwd");
   return ANR_OK;
+}
+
+extern "C" int anr_composite_ref16_bwd(const float* z, float z_scale, const void* color,
+                                       const void* sigma, const void* color_surf,
+                                       int32_t in_dtype, int64_t B, int32_t N, int32_t C,
+                                       const void* d_color_map, void* d_color, void* d_sigma,
+                                       void* d_color_surf, int32_t out_dtype, int32_t* zero_rays,
+                                       anr_stream_t stream) {
+  ANR_CHECK_ARG(sigma, "anr_composite_ref16_bwd: null argument");
+  return composite_ref16_bwd(z, z_scale, color, sigma, color_surf, in_dtype, B, N, C,
+                             d_color_map, d_color, d_sigma, d_color_surf, out_dtype, zero_rays,
+                             nullptr, nullptr, stream);
+}
+
+extern "C" int anr_composite_ref16_bwd_parked(const float* z, float z_scale, const void* color,
+                                              const void* sigma, const void* color_surf,
+                                              int32_t in_dtype, int64_t B, int32_t N, int32_t C,
+                                              const void* d_color_map, void* d_color,
+                                              void* d_sigma, void* d_color_surf,
+                                              int32_t out_dtype, int32_t* zero_rays,
+                                              const uint32_t* park, const uint32_t* ray_park,
+                                              anr_stream_t stream) {
+  ANR_CHECK_ARG(park && ray_park, "anr_composite_ref16_bwd_parked: null park");
+  return composite_ref16_bwd(z, z_scale, color, sigma, color_surf, in_dtype, B, N, C,
+                             d_color_map, d_color, d_sigma, d_color_surf, out_dtype, zero_rays,
+                             park, ray_park, stream);
 }
 
 extern "C" int anr_loss_ref16_fwd_bwd(int32_t loss_type, const void* color_map, int32_t C,

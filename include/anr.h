@@ -36,7 +36,9 @@ extern "C" {
  * ABI 5 (r06): anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and its workspace size;
  * added since without a version change (additive): anr_ingp_field_fwd_h,
  * anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16 interchange between the
- * field and the f16 composite).
+ * field and the f16 composite); anr_composite_ref16_fwd_park and
+ * anr_composite_ref16_bwd_parked (the forward parks T, exp and the surface product for its
+ * backward, which then skips its replay of the forward).
  * ABI 4 (r06): anr_ingp_hash_field_fwd. ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused
  * field entry points' enc_stride < 0
  * selecting the level-quad-plane layout it writes. */
@@ -616,6 +618,28 @@ int anr_composite_ref16_bwd(const float* z, float z_scale, const void* color,
                             int64_t B, int32_t N, int32_t C, const void* d_color_map,
                             void* d_color, void* d_sigma, void* d_color_surf,
                             int32_t out_dtype, int32_t* zero_rays, anr_stream_t stream);
+/* The pair a training step runs: the forward also parks what the backward would otherwise
+ * recompute from z and sigma, and the backward reads it back instead of replaying the
+ * forward (no first pass, sigma is not read and may be null, d_color / d_sigma are outputs
+ * only). Same arguments, outputs and gradients as the two entry points above, bit for bit.
+ * park (B*N): per sample the f16 bits of T_i (the cumprod output, low half) and of
+ * exp(-sigma_i delta_i) (high half). ray_park (B): the f16 bits of the surface product
+ * prod(1 - alpha) in the low half, bit 16 set when an alpha of the ray rounded to exactly 1
+ * (the rays zero_rays counts). Both required, 4-byte aligned, independent of the dtypes;
+ * a park is valid only for the z / color / sigma / color_surf it was written from. */
+int anr_composite_ref16_fwd_park(const float* z, float z_scale, const void* color,
+                                 const void* sigma, const void* color_surf, int32_t in_dtype,
+                                 int64_t B, int32_t N, int32_t C, void* color_map,
+                                 void* color_map_atmo, void* color_map_surf, void* weights,
+                                 void* alpha, void* color16, void* sigma16, uint32_t* park,
+                                 uint32_t* ray_park, anr_stream_t stream);
+int anr_composite_ref16_bwd_parked(const float* z, float z_scale, const void* color,
+                                   const void* sigma, const void* color_surf,
+                                   int32_t in_dtype, int64_t B, int32_t N, int32_t C,
+                                   const void* d_color_map, void* d_color, void* d_sigma,
+                                   void* d_color_surf, int32_t out_dtype, int32_t* zero_rays,
+                                   const uint32_t* park, const uint32_t* ray_park,
+                                   anr_stream_t stream);
 /* Loss in f16 ops: color_map (B,C) f16, gt (B,) f32 (cast to f16 as instant_ngp.py:262),
  * loss_out: 1 f32 holding the f16 loss value, grad_out (B,C) f16 (nullable),
  * workspace >= anr_loss_workspace_bytes(B). */

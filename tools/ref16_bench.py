@@ -3,7 +3,7 @@ bench shape (profiling aid): 8,192 rays x 1,024 samples x 4 bands, atmospheric s
 f16 inputs as the field writes them, surface colour on. HIP-event averages of 10 warm
 launches each.
 
-    python tools/ref16_bench.py [--rays 8192] [--samples 1024]
+    python tools/ref16_bench.py [--rays 8192] [--samples 1024] [--rays-per-wave 0]
 """
 
 import argparse
@@ -25,7 +25,10 @@ def main():
     ap.add_argument("--rays", type=int, default=8192)
     ap.add_argument("--samples", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--rays-per-wave", type=int, default=0,
+                    help="anr_composite_ref16_set_rays: 0 (the default rule), 1, 2, 4 or 8")
     a = ap.parse_args()
+    _lib.call("anr_composite_ref16_set_rays", a.rays_per_wave)
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     B, N = a.rays, a.samples

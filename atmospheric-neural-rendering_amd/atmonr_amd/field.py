@@ -23,6 +23,12 @@ With f16 networks of the shapes both reference configs use (pos 32->W->16, dir 1
 (anr_ingp_field_fwd/bwd): pos_out and dL/dpos_out stay in registers, the backward writes
 only dL/denc. The weights are packed into MFMA fragment order once per forward. bf16
 networks (BASELINE configs[4]: f16 hash features, bf16 MFMA MLP) run only this way.
+
+multi_band_extinction (S = num_bands <= 4 density outputs; the dir network then has 20 - S
+inputs): the same fused kernels with sigma and d_sigma (M, S) row-major, build numerics
+and dense rows only -- never the hash-field kernel, the f16-output forward or the rows
+(occupancy) forms, which stay at one density output. The semi-fused f32 branch below is
+not extended; the pipeline does not route S > 1 to it.
 The backward's workspace (per-wavefront f16 gradient maxima) is allocated here, through
 torch's caching allocator, at anr_ingp_field_bwd_workspace_bytes.
 
@@ -83,6 +89,11 @@ class IngpFieldFn(torch.autograd.Function):
         ctx.params = (p_hash, p_pos, p_dir)
         ctx.rows = rows
         planes = fused and _enc_planes(grid, M)
+        n_sig = n_density(pipe)
+        if n_sig > 1 and not (fused and rows is None and
+                              getattr(pipe, "numerics", "build") == "build"):
+            raise _lib.ANRError("multi-band extinction runs the fused field in build numerics "
+                                "without occupancy culling")
         if fused:
             mma = _mma_code(pipe)
             pdesc, ddesc = ctypes.byref(pos_mod.desc), ctypes.byref(pipe.dir_mlp.desc)
@@ -92,7 +103,7 @@ class IngpFieldFn(torch.autograd.Function):
             call("anr_ingp_field_pack", pdesc, ddesc, mma, ptr(m_pos), ptr(m_dir), ptr(packed),
                  s, tag="field_pack")
             nb = pipe.dir_mlp.n_output_dims
-        if planes and rows is None and _hash_field_ok(grid, nb, n_per_ray):
+        if planes and rows is None and n_sig == 1 and _hash_field_ok(grid, nb, n_per_ray):
             # hash grid + field forward in one kernel (anr_ingp_hash_field_fwd): the level-
             # quad planes are written for the backward and never re-read by the forward
             nq = (grid.desc.n_levels + 3) // 4
@@ -105,6 +116,7 @@ class IngpFieldFn(torch.autograd.Function):
                  ptr(packed), ptr(dirs), n_per_ray, ptr(sigma), ptr(color), color.stride(0), s,
                  tag="hash_field_fwd")
             ctx.fused_field = True
+            ctx.n_sig = 1
             ctx.save_for_backward(coords, dirs, enc, packed)
             return sigma, color
         if planes:
@@ -135,7 +147,9 @@ class IngpFieldFn(torch.autograd.Function):
                      ptr(dirs), n_per_ray, M, ptr(sigma), ptr(color), color.stride(0), s,
                      tag="field_fwd")
             elif rows is None:
-                sigma = torch.empty(M, device=dev, dtype=torch.float32)
+                # one density per sample, or (M, S) with multi-band extinction
+                sigma = torch.empty((M,) if n_sig == 1 else (M, n_sig), device=dev,
+                                    dtype=torch.float32)
                 color = torch.empty(M, nb, device=dev, dtype=torch.float32)
                 call("anr_ingp_field_fwd", pdesc, ddesc, mma, ptr(packed), ptr(enc), enc_ld,
                      ptr(dirs), n_per_ray, M, ptr(sigma), ptr(color), color.stride(0), s,
@@ -147,9 +161,11 @@ class IngpFieldFn(torch.autograd.Function):
                      enc_ld, ptr(dirs), n_per_ray, M, ptr(rows), ptr(sigma), ptr(color),
                      color.stride(0), s, tag="field_fwd")
             ctx.fused_field = True
+            ctx.n_sig = n_sig
             ctx.save_for_backward(coords, dirs, enc, packed)
             return sigma, color
         ctx.fused_field = False
+        ctx.n_sig = 1
         w_pos = _lib.compute_copy(p_pos, cdt)
         w_dir = _lib.compute_copy(p_dir, cdt)
         pos_out = torch.empty(M, pos_mod.n_output_dims, device=dev, dtype=torch.float32)
@@ -229,6 +245,8 @@ class IngpFieldFn(torch.autograd.Function):
         else:
             d_color = d_color.float().contiguous()
             d_sigma = d_sigma.float().contiguous() if d_sigma is not None else None
+        if ctx.n_sig > 1 and d_sigma is None:  # (M, S) f32, as the kernel reads it
+            d_sigma = torch.zeros(M, ctx.n_sig, device=dev)
         pdesc, ddesc = ctypes.byref(pipe.pos_mlp.desc), ctypes.byref(pipe.dir_mlp.desc)
         mma = _mma_code(pipe)
         tiles = row_nz = None
@@ -340,6 +358,12 @@ _POS_PASS = os.environ.get("ANR_POS_PASS", "1") != "0"
 _REF_F16_IO = os.environ.get("ANR_REF_F16_IO", "1") != "0"
 
 
+def n_density(pipe) -> int:
+    """Density outputs S of the pipeline's field: pos_out[:, :S] (1, or num_bands with
+    multi_band_extinction); the dir network's 20 - S inputs say so to the kernels."""
+    return int(getattr(pipe, "num_density_outputs", 1))
+
+
 def field_fused(pipe) -> bool:
     """True when the pipeline's networks run through anr_ingp_field_{fwd,bwd}."""
     flag = getattr(pipe, "_field_fused", None)
@@ -359,7 +383,8 @@ def field_fused(pipe) -> bool:
 
 @torch.no_grad()
 def field_density(pipe, pts: torch.Tensor, run_length: int = 0) -> torch.Tensor:
-    """sigma = relu(pos_mlp(pos_encoder(pts))[:, 0]) at hash-grid points (P, 3) ((P, 4) for a
+    """sigma = relu(pos_mlp(pos_encoder(pts))[:, 0]) ((P, S): [:, :S] with S > 1 density
+    outputs, multi_band_extinction) at hash-grid points (P, 3) ((P, 4) for a
     4-D grid: anr_append_heights rows) through the
     fused kernels (hash forward, then anr_ingp_field_density: the pos MLP of
     anr_ingp_field_fwd without the dir MLP, bit-identical sigma). The extract path of
@@ -370,7 +395,8 @@ def field_density(pipe, pts: torch.Tensor, run_length: int = 0) -> torch.Tensor:
     dev = pts.device
     s = _lib.stream(dev)
     P = pts.shape[0]
-    sigma = torch.empty(P, device=dev, dtype=torch.float32)
+    n_sig = n_density(pipe)
+    sigma = torch.empty((P,) if n_sig == 1 else (P, n_sig), device=dev, dtype=torch.float32)
     if P == 0:
         return sigma
     enc_mod, pos_mod = pipe.pos_encoder, pipe.pos_mlp

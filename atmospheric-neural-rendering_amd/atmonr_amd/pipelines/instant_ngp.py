@@ -30,6 +30,17 @@ the position grid is 4-D and every sample's normalised ellipsoidal height is its
 coordinate (instant_ngp.py:50,153,227); the results gain ``norm_heights_fine``. The fused
 path computes the height inside the sampler kernel, the unfused path and ``extract`` with
 anr_append_heights. Build numerics only, no occupancy grid (its cells are 3-D).
+
+``multi_band_extinction: true``: the first ``num_bands`` outputs of ``pos_mlp`` are
+per-band extinctions (instant_ngp.py:46-48,178,184), the dir encoder takes
+``3 + 16 - num_bands`` inputs (:64-77) and the composite runs one density per band;
+``sigma_fine`` is ``(B, N-1, num_bands)`` and ``extract`` returns ``(P, num_bands)``. With
+up to four bands, f16 hash tables, f16 or bf16 field MLPs, build numerics and no occupancy
+grid it runs the fused path (the fused field kernels with S = num_bands density outputs,
+the fused ``extract``); otherwise (f32 modules, more than four bands, an occupancy grid)
+the op-by-op path, as ``fused=False`` does. ``numerics="reference"`` does not take it (the
+f16 composite has one density channel). With ``include_height`` it runs as well: the field
+kernels do not see the grid's dimension.
 """
 
 from __future__ import annotations
@@ -82,11 +93,16 @@ class InstantNGPPipeline(Pipeline):
                                     (self.config.get("occupancy_grid") and numerics == "build")):
             raise ValueError("include_height does not combine with the occupancy grid "
                              "(its cells are 3-D)")
-        if fused and self.num_density_outputs != 1:
-            fused = False
-        self.fused = fused
         self.dtype = dtype
         mlp_dtype = dtype if mlp_dtype is None else mlp_dtype
+        if fused and self.num_density_outputs != 1:
+            # multi-band extinction stays fused where the native field takes the pair (up
+            # to four bands; checked against the descriptors below), on f16 hash tables
+            # with f16 / bf16 field MLPs, in build numerics, without an occupancy grid
+            fused = (self.num_density_outputs <= 4 and dtype == torch.float16
+                     and mlp_dtype in (torch.float16, torch.bfloat16) and numerics == "build"
+                     and occupancy is None and not self.config.get("occupancy_grid"))
+        self.fused = fused
         if mlp_dtype == torch.bfloat16 and (dtype != torch.float16 or not fused):
             raise ValueError("bf16 field MLPs need f16 hash features and the fused path")
         self.mlp_dtype = mlp_dtype
@@ -104,10 +120,6 @@ class InstantNGPPipeline(Pipeline):
         self.surface_stream = os.environ.get("ANR_SURFACE_STREAM", "1") != "0"
         ingp = self.config["instant_ngp"]
         nb = self.config["num_bands"]
-        # the fused path keeps activations / gradients in f32 (build numerics); tcnn's f16
-        # outputs in reference numerics: the per-ray surface modules here, and the fused
-        # field's sigma / colour and their gradients (field.py, ANR_REF_F16_IO)
-        fdt = torch.float32 if fused and numerics == "build" else None
         self.pos_encoder = Encoding(4 if self.include_height else 3, ingp["encoding"], seed=seed,
                                     dtype=dtype)
         self.pos_mlp = Network(self.pos_encoder.n_output_dims, 16, ingp["network"],
@@ -116,6 +128,16 @@ class InstantNGPPipeline(Pipeline):
                                     seed=seed + 2, dtype=dtype)
         self.dir_mlp = Network(self.dir_encoder.n_output_dims, nb, ingp["rgb_network"],
                                seed=seed + 3, dtype=mlp_dtype)
+        if self.fused and self.num_density_outputs != 1 and not field_fused(self):
+            # the native field refuses the pair (its widths / depths): the op-by-op path
+            if mlp_dtype == torch.bfloat16:
+                raise ValueError("bf16 field MLPs need f16 hash features and the fused path")
+            self.fused = fused = False
+            self._field_fused = None  # field_fused() caches per pipeline: ask again
+        # the fused path keeps activations / gradients in f32 (build numerics); tcnn's f16
+        # outputs in reference numerics: the per-ray surface modules here, and the fused
+        # field's sigma / colour and their gradients (field.py, ANR_REF_F16_IO)
+        fdt = torch.float32 if fused and numerics == "build" else None
         self.surf_encoder = Encoding(2 + 3, ingp["surface_encoding"], seed=seed + 4,
                                      dtype=dtype, output_dtype=fdt)
         self.surf_mlp = Network(self.surf_encoder.n_output_dims, nb, ingp["surface_network"],
@@ -258,7 +280,7 @@ class InstantNGPPipeline(Pipeline):
             sigma, color = IngpFieldFn.apply(coords.view(B * N, coords.shape[-1]),
                                              ray_batch["dir"].float(), N, *params)
         color = color.view(B, N, -1)
-        sigma = sigma.view(B, N, 1)
+        sigma = sigma.view(B, N, self.num_density_outputs)
         color_surf = surf_branch()
         if self.numerics == "reference":
             if self._zero_rays is None:  # counts over the pipeline's life (no per-step op)
@@ -346,12 +368,11 @@ class InstantNGPPipeline(Pipeline):
         else:
             pts = (pts + 1) / 2
             pts[..., 2] = pts[..., 2] / self.alt_compress
-        if self.num_density_outputs == 1 and field_fused(self) and \
-                self.pos_encoder.dtype == torch.float16:
-            # the fused field's sigma output IS relu(pos_out[:, 0]) (f32 accumulator);
+        if field_fused(self) and self.pos_encoder.dtype == torch.float16:
+            # the fused field's sigma output IS relu(pos_out[:, :S]) (f32 accumulator);
             # returned in tcnn's output precision, as the reference's clip of pos_out
-            return field_density(self, pts, run_length).view(pts.shape[0], 1).to(
-                self.pos_mlp.output_dtype)
+            return field_density(self, pts, run_length).view(
+                pts.shape[0], self.num_density_outputs).to(self.pos_mlp.output_dtype)
         with torch.no_grad():
             pos_out = self.pos_mlp(self.pos_encoder(pts))
         return torch.clip(pos_out[..., : self.num_density_outputs].view(

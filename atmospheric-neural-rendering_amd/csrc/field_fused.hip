@@ -6,6 +6,11 @@
 //   x_dir   = [SH2(dir) | pos_out[:, 1:16] | 1.0 ...]              (:165-169)
 //   color   = relu(dir_mlp(x_dir))               32 -> W (x NHD) -> 16  (:170-171,183)
 //
+// multi_band_extinction (S = 2..4 density outputs, :46-48): sigma = relu(pos_out[:, :S]),
+// x_dir = [SH2(dir) | pos_out[:, S:16] | 1.0 ...] with 20 - S inputs. S is a compile-time
+// parameter of the kernels (S = 20 - dir.n_input); the S = 1 instantiations are the code
+// they were before it existed.
+//
 // Layers are evaluated in transposed form on v_mfma_f32_16x16x32_f16, out^T = W · in^T,
 // with 16 samples as the MFMA's N dimension. The C tile of one layer (lane = sample
 // l&15, units 4(l>>4)+i of each 16-unit block) is, after ReLU and f16 conversion, the B
@@ -144,20 +149,35 @@ __host__ __device__ constexpr int perm32(int k) {
 // Dir-MLP input slot k' -> tcnn input column. Lane group g holds pos_out[4g..4g+3] in
 // slots 8g..8g+3 (pos_out[p] is column p+3; slot 0 carries a 1.0 padding column instead
 // of pos_out[0] = density), and SH2 (g = 0) or more 1.0 padding (g > 0) in 8g+4..8g+7.
+// With S density outputs pos_out[p >= S] is column 4 + p - S and the S slots of the
+// densities carry 1.0 padding like the 12 of g > 0: for S <= 3 (rows 32 wide) the 12 + S
+// padding slots map one to one onto the padding columns 20 - S .. 31; for S = 4 the rows
+// are 16 wide, all of them real inputs, and a padding slot has no column (-1: zero weight
+// in the fragments, its dW sum dropped).
+template <int S>
 __host__ __device__ constexpr int dir_col(int k) {
   const int g = k >> 3, j = k & 7;
-  return j < 4 ? ((g == 0 && j == 0) ? 19 : 4 * g + j + 3) : (g == 0 ? j - 4 : 20 + 4 * (g - 1) + (j - 4));
+  if constexpr (S == 1) {
+    return j < 4 ? ((g == 0 && j == 0) ? 19 : 4 * g + j + 3) : (g == 0 ? j - 4 : 20 + 4 * (g - 1) + (j - 4));
+  } else {
+    if (j >= 4) return g == 0 ? j - 4 : (S == 4 ? -1 : 20 + 4 * (g - 1) + (j - 4));
+    const int p = 4 * g + j;
+    return p < S ? (S == 4 ? -1 : 20 - S + p) : 4 + p - S;
+  }
 }
 
-template <int W, int NHD>
+template <int W, int NHD, int S = 1>
 struct Net {
+  static_assert(S >= 1 && S <= 4, "1 to 4 density outputs");
+  // width of the first dir layer's parameter rows: n_input_padded of 20 - S inputs
+  static constexpr int LD0 = S == 4 ? 16 : 32;
   static_assert(W == 32 || W == 64, "width 32 or 64");
   static_assert(NHD == 1 || NHD == 2, "1 or 2 dir hidden layers");
   static constexpr int NT = W / 16, KB = W / 32;
   static constexpr int F32 = 512, F16 = 256;  // halves per 16x16x32 / 16x16x16 A fragment
   // parameter offsets (tcnn order, each layer row-major [out][in])
   static constexpr int P0 = 0, P1 = 32 * W, NPOS = 32 * W + 16 * W;
-  static constexpr int D0 = 0, D1 = 32 * W, D2 = 32 * W + (NHD - 1) * W * W;
+  static constexpr int D0 = 0, D1 = LD0 * W, D2 = LD0 * W + (NHD - 1) * W * W;
   static constexpr int NDIR = D2 + 16 * W;
   // packed fragment offsets (halves): forward A = W, backward A = W^T
   static constexpr int oFP0 = 0;                                  // [NT]
@@ -188,10 +208,10 @@ struct Net {
 // ---------------------------------------------------------------------------------
 // weight packing (f32 master params -> f16 fragments)
 // ---------------------------------------------------------------------------------
-template <int W, int NHD, bool BF>
+template <int W, int NHD, bool BF, int S = 1>
 __global__ void pack_kernel(const float* __restrict__ pp, const float* __restrict__ pd,
                             _Float16* __restrict__ out) {
-  using N = Net<W, NHD>;
+  using N = Net<W, NHD, S>;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= N::n_packed) return;
   int f, r, k;
@@ -219,7 +239,12 @@ __global__ void pack_kernel(const float* __restrict__ pp, const float* __restric
     v = pp[N::P1 + r * W_ + 32 * f + perm32(k)];
   } else if (e < N::oFD1) {
     frag32(N::oFD0);
-    v = pd[N::D0 + (16 * f + r) * 32 + dir_col(k)];
+    if constexpr (S == 1) {
+      v = pd[N::D0 + (16 * f + r) * 32 + dir_col<1>(k)];
+    } else {
+      const int c = dir_col<S>(k);
+      v = c < 0 ? 0.0f : pd[N::D0 + (16 * f + r) * N::LD0 + c];
+    }
   } else if (e < N::oFD2) {
     frag32(N::oFD1);
     const int nt = f / N::KB, kb = f - nt * N::KB;
@@ -236,7 +261,11 @@ __global__ void pack_kernel(const float* __restrict__ pp, const float* __restric
     v = pd[N::D1 + (32 * kb + perm32(k)) * W_ + 16 * kt + r];
   } else if (e < N::oBP1) {
     frag32(N::oBD0);
-    v = r == 0 ? 0.0f : pd[N::D0 + (32 * f + perm32(k)) * 32 + r + 3];
+    // row r = pos_out unit r: its column of the dir input (the densities have none)
+    if constexpr (S == 1)
+      v = r == 0 ? 0.0f : pd[N::D0 + (32 * f + perm32(k)) * 32 + r + 3];
+    else
+      v = r < S ? 0.0f : pd[N::D0 + (32 * f + perm32(k)) * N::LD0 + 4 + r - S];
   } else if (e < N::oBP0) {
     frag16(N::oBP1);
     v = pp[N::P1 + k * W_ + 16 * f + r];
@@ -390,7 +419,7 @@ struct Rows {
   float ds;       // dL/dsigma[row] (backward, g == 0 lanes)
 };
 
-template <bool ROWS, bool HG = false>
+template <bool ROWS, bool HG = false, int S = 1>
 __device__ __forceinline__ void load_rows(const Args& a, int64_t row, int g, bool bwd, Rows& in) {
   in.xe = h8{};
   in.dx = in.dy = in.dz = 0.0f;
@@ -405,7 +434,9 @@ __device__ __forceinline__ void load_rows(const Args& a, int64_t row, int g, boo
     in.dx = d[0] * 2.0f - 1.0f;
     in.dy = d[1] * 2.0f - 1.0f;
     in.dz = d[2] * 2.0f - 1.0f;
-    if constexpr (HG) {
+    if constexpr (S > 1) {
+      static_assert(!HG, "S > 1: f32 gradients");  // load_dsig() loads the S values
+    } else if constexpr (HG) {
       if (bwd && a.d_sigma_h) in.ds = static_cast<float>(a.d_sigma_h[drow]);
     } else {
       if (bwd && a.d_sigma) in.ds = a.d_sigma[drow];
@@ -436,14 +467,29 @@ __device__ __forceinline__ void load_rows(const Args& a, int64_t row, int g, boo
   }
 }
 
+// S > 1: dL/dsigma[row][0 .. S-1] of the dense row (load_rows's in.ds stays 0); unused
+// slots, rows past M and a null d_sigma give 0.
+template <bool ROWS, int S>
+__device__ __forceinline__ f4 load_dsig(const Args& a, int64_t row) {
+  f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (row < a.M && a.d_sigma) {
+    const int64_t drow = dense_row<ROWS>(a, row);
+#pragma unroll
+    for (int j = 0; j < S; ++j) v[j] = a.d_sigma[drow * S + j];
+  }
+  return v;
+}
+
 // Input row of the dir MLP for the sample in this lane (B-operand slots 8g..8g+7).
 // Branch-free (per-lane selects): a divergent branch here gives the compiler a place to
 // merge other g == 0 code into, including uses of the backward's prefetched loads, which
 // then wait for those loads at once.
-template <bool BF>
+// S density outputs: slots j < S of g == 0 carry 1.0 in place of pos_out[j].
+template <bool BF, int S = 1>
 __device__ __forceinline__ h8 dir_input(const Rows& in, bool valid, int g, f4 po) {
   const _Float16 one = cvt1<BF>(1.0f);
-  const h8 lead = {one, cvt1<BF>(po[1]), cvt1<BF>(po[2]), cvt1<BF>(po[3]),
+  const h8 lead = {one, S > 1 ? one : cvt1<BF>(po[1]), S > 2 ? one : cvt1<BF>(po[2]),
+                   S > 3 ? one : cvt1<BF>(po[3]),
                    cvt1<BF>(0.28209479177387814f), cvt1<BF>(-0.48860251190291987f * in.dy),
                    cvt1<BF>(0.48860251190291987f * in.dz), cvt1<BF>(-0.48860251190291987f * in.dx)};
   const h8 rest = {cvt1<BF>(po[0]), cvt1<BF>(po[1]), cvt1<BF>(po[2]), cvt1<BF>(po[3]), one, one,
@@ -521,7 +567,7 @@ struct NoSink {
 // to LDS there, so they need not stay live in registers)
 // dir = false (wave-uniform): the pos network only; col = 0 (the backward of a tile whose
 // dL/dcolor is zero in every row needs nothing of the dir network)
-template <int W, int NHD, int NM, bool BF, typename WS, typename SK>
+template <int W, int NHD, int NM, bool BF, int S, typename WS, typename SK>
 __device__ __forceinline__ void tile_forward(const WS& fw, const Rows* in, const bool* valid,
                                              int g, Tile<W, NHD>* t, const SK& sink,
                                              bool dir = true) {
@@ -556,7 +602,7 @@ __device__ __forceinline__ void tile_forward(const WS& fw, const Rows* in, const
   }
 #pragma unroll
   for (int mt = 0; mt < NM; ++mt) {
-    t[mt].xd = dir_input<BF>(in[mt], valid[mt], g, t[mt].po);
+    t[mt].xd = dir_input<BF, S>(in[mt], valid[mt], g, t[mt].po);
     sink.xd(mt, t[mt].xd);
   }
 #pragma unroll
@@ -643,6 +689,7 @@ __device__ __forceinline__ void fwd_raw_to_rows(const FwdRaw& r, Rows& in) {
 // one prefetch round trip per tile.
 typedef uint32_t u4v __attribute__((vector_size(16)));
 typedef uint32_t u2v __attribute__((vector_size(8)));
+typedef uint32_t u3v __attribute__((ext_vector_type(3)));
 typedef __attribute__((address_space(4))) const float const_f32;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(const void* p, int64_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, static_cast<int>(bytes),
@@ -658,10 +705,32 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(const void* p, int64_
 // the f32 value of the f32 form rounded to nearest even after its max(., 0). The
 // uniform-tile form keeps its shape: one 2-byte sigma and one 8-byte colour buffer store
 // per lane and tile, and the same two dropped stores ahead of the loop.
-template <int W, int NHD, bool ROWS, bool BF, bool UT, bool HO = false>
+//
+// S > 1 (multi-band extinction, f32 outputs, dense rows): sigma is (M, S) row-major and the
+// g == 0 lane stores its row's S values relu(pos_out[0 .. S-1]) -- its own four accumulator
+// registers -- as one store (8 / 12 / 16 bytes).
+typedef float f2 __attribute__((ext_vector_type(2)));
+struct f3s {
+  float x, y, z;
+};
+template <int S>
+__device__ __forceinline__ void store_sigma(float* p, const f4& po) {
+  if constexpr (S == 1) {
+    p[0] = fmaxf(po[0], 0.0f);
+  } else if constexpr (S == 2) {
+    *reinterpret_cast<f2*>(p) = f2{fmaxf(po[0], 0.0f), fmaxf(po[1], 0.0f)};
+  } else if constexpr (S == 3) {
+    *reinterpret_cast<f3s*>(p) = f3s{fmaxf(po[0], 0.0f), fmaxf(po[1], 0.0f), fmaxf(po[2], 0.0f)};
+  } else {
+    *reinterpret_cast<f4*>(p) =
+        f4{fmaxf(po[0], 0.0f), fmaxf(po[1], 0.0f), fmaxf(po[2], 0.0f), fmaxf(po[3], 0.0f)};
+  }
+}
+template <int W, int NHD, bool ROWS, bool BF, bool UT, bool HO = false, int S = 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) fwd_kernel(Args a) {
   static_assert(!(UT && ROWS), "the uniform-tile form needs dense rows");
   static_assert(!(HO && ROWS), "f16 outputs: dense rows only");
+  static_assert(S == 1 || !(HO || ROWS), "S > 1: f32 outputs, dense rows");
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   // wave index through readfirstlane: the tile loop then runs on scalar registers
   const int waves = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -690,7 +759,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
         }
         return;
       }
-      if (g == 0) a.sigma[drow] = fmaxf(t.po[0], 0.0f);
+      if constexpr (S == 1) {
+        if (g == 0) a.sigma[drow] = fmaxf(t.po[0], 0.0f);
+      } else {
+        if (g == 0) store_sigma<S>(a.sigma + drow * S, t.po);
+      }
       if (c0 + 3 < a.n_out && (a.color_stride & 3) == 0) {
         f4 v;
 #pragma unroll
@@ -706,13 +779,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
   auto body = [&](const Rows& cur, int64_t row) {
     Tile<W, NHD> t;
     const bool valid = row < a.M;
-    tile_forward<W, NHD, 1, BF>(fw, &cur, &valid, g, &t, NoSink{});
+    tile_forward<W, NHD, 1, BF, S>(fw, &cur, &valid, g, &t, NoSink{});
     store(t, row);
   };
   if constexpr (UT) {
     constexpr uint32_t ES = HO ? 2u : 4u;  // bytes per output element
     const __amdgpu_buffer_rsrc_t rsig =
-        HO ? out_rsrc(a.sigma_h, a.M * ES) : out_rsrc(a.sigma, a.M * ES);
+        HO ? out_rsrc(a.sigma_h, a.M * ES) : out_rsrc(a.sigma, a.M * ES * S);
     const __amdgpu_buffer_rsrc_t rcol = HO ? out_rsrc(a.color_h, a.M * a.color_stride * ES)
                                            : out_rsrc(a.color, a.M * a.color_stride * ES);
     const uint32_t cs_bytes = static_cast<uint32_t>(a.color_stride) * ES;
@@ -752,9 +825,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
       nxe = *enc_ptr(tn);
       Tile<W, NHD> t;
       const bool valid = true;
-      tile_forward<W, NHD, 1, BF>(fw, &cur, &valid, g, &t, NoSink{});
+      tile_forward<W, NHD, 1, BF, S>(fw, &cur, &valid, g, &t, NoSink{});
       const uint32_t row = static_cast<uint32_t>(tile * 16 + li);
-      const uint32_t so = g == 0 ? row * ES : 0x80000000u;
+      const uint32_t so = g == 0 ? row * (ES * S) : 0x80000000u;
       const uint32_t co = g == 0 ? row * cs_bytes : 0x80000000u;
       if constexpr (HO) {
         const _Float16 sh = static_cast<_Float16>(fmaxf(t.po[0], 0.0f));
@@ -765,7 +838,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) f
                                               0, 0);
         continue;
       }
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(t.po[0], 0.0f)), rsig, so, 0, 0);
+      if constexpr (S == 1) {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(t.po[0], 0.0f)), rsig, so, 0, 0);
+      } else {  // the row's S densities, one store
+        const uint32_t s0 = __float_as_uint(fmaxf(t.po[0], 0.0f));
+        const uint32_t s1 = __float_as_uint(fmaxf(t.po[1], 0.0f));
+        const uint32_t s2 = __float_as_uint(fmaxf(t.po[2], 0.0f));
+        const uint32_t s3 = __float_as_uint(fmaxf(t.po[3], 0.0f));
+        if constexpr (S == 2)
+          __builtin_amdgcn_raw_buffer_store_b64(u2v{s0, s1}, rsig, so, 0, 0);
+        else if constexpr (S == 3)
+          __builtin_amdgcn_raw_buffer_store_b96(u3v{s0, s1, s2}, rsig, so, 0, 0);
+        else
+          __builtin_amdgcn_raw_buffer_store_b128(u4v{s0, s1, s2, s3}, rsig, so, 0, 0);
+      }
       const u4v v = {__float_as_uint(fmaxf(t.col[0], 0.0f)), __float_as_uint(fmaxf(t.col[1], 0.0f)),
                      __float_as_uint(fmaxf(t.col[2], 0.0f)), __float_as_uint(fmaxf(t.col[3], 0.0f))};
       __builtin_amdgcn_raw_buffer_store_b128(v, rcol, co, 0, 0);
@@ -880,7 +966,7 @@ hf_fwd_kernel(Args a, HashArgs h) {
       asm volatile("" : "+v"(zoff));
       const LdsWeights<W, NHD> fw{wsm + zoff, lane};
       Tile<W, NHD> tt;
-      tile_forward<W, NHD, 1, BF>(fw, &cur, &valid, g, &tt, NoSink{});
+      tile_forward<W, NHD, 1, BF, 1>(fw, &cur, &valid, g, &tt, NoSink{});
       const uint32_t so = g == 0 && valid ? row * 4u : 0x80000000u;
       const uint32_t co = g == 0 && valid ? row * cs_bytes : 0x80000000u;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(fmaxf(tt.po[0], 0.0f)), rsig, so, 0, 0);
@@ -927,7 +1013,7 @@ __device__ __forceinline__ void st4g(_Float16* base, int ld, int mrow, int col, 
 // extinction is read) and the occupancy grid's density. The same MFMA sequence as the
 // full forward's pos half, so sigma is bit-identical to anr_ingp_field_fwd's. Weights in
 // registers, one 16-row tile per wavefront step, the next tile's encodings in flight.
-template <int W, int NHD, bool BF>
+template <int W, int NHD, bool BF, int S = 1>
 __global__ void __launch_bounds__(256) density_kernel(Args a) {
   using N = Net<W, NHD>;
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
@@ -960,7 +1046,11 @@ __global__ void __launch_bounds__(256) density_kernel(Args a) {
 #pragma unroll
     for (int kb = 0; kb < N::KB; ++kb) po = mma32<BF>(p1[kb], cat(hp[2 * kb], hp[2 * kb + 1]), po);
     const int64_t row = tile * 16 + li;
-    if (g == 0 && row < a.M) a.sigma[row] = fmaxf(po[0], 0.0f);
+    if constexpr (S == 1) {
+      if (g == 0 && row < a.M) a.sigma[row] = fmaxf(po[0], 0.0f);
+    } else {
+      if (g == 0 && row < a.M) store_sigma<S>(a.sigma + row * S, po);
+    }
   }
 }
 
@@ -975,11 +1065,22 @@ __device__ __forceinline__ float wave_grad_max(const Args& a, const float* wmax,
 // Rows of the backward's wavefront w: tiles [w*tpw, (w+1)*tpw) of 32 rows. The f16
 // gradient scale of a wavefront is set from max(|dL/dcolor|, |dL/dsigma|) over its rows,
 // which this kernel computes first (one block per wavefront range, full occupancy).
-template <bool ROWS>
+// S > 1: dL/dsigma is (M, S) and the maximum runs over all S columns.
+template <bool ROWS, int S = 1>
 __global__ void __launch_bounds__(1024) absmax_kernel(Args a, int64_t rows_per_wave, float* wmax) {
   const int64_t r0 = static_cast<int64_t>(blockIdx.x) * rows_per_wave;
   const int64_t r1 = r0 + rows_per_wave < a.M ? r0 + rows_per_wave : a.M;
   float m = 0.0f;
+  if constexpr (S > 1) {
+    for (int64_t rr = r0 + threadIdx.x; rr < r1; rr += blockDim.x) {
+      const int64_t r = dense_row<ROWS>(a, rr);
+      for (int c = 0; c < a.n_out; ++c) m = fmaxf(m, fabsf(a.d_color[r * a.d_color_stride + c]));
+      if (a.d_sigma) {
+#pragma unroll
+        for (int j = 0; j < S; ++j) m = fmaxf(m, fabsf(a.d_sigma[r * S + j]));
+      }
+    }
+  } else
   if (a.n_out == 4 && (a.d_color_stride & 3) == 0) {
     // four rows per thread per iteration, loads issued before any max (one wait each)
     const int64_t step = blockDim.x;
@@ -1030,16 +1131,24 @@ __global__ void __launch_bounds__(1024) absmax_kernel(Args a, int64_t rows_per_w
 // HG (f16 gradients, a.d_sigma_h / a.d_color_h): the row's dL/dcolor is one 8-byte load and
 // its dL/dsigma a 2-byte load (zero-extended into a 32-bit register), converted to f32 --
 // exactly -- by raw_to_rows() like the rest.
-template <bool HG>
-struct RawRowsT {
+// S > 1 (f32 gradients): the row's S values of dL/dsigma in dsb (an empty base at S = 1,
+// so that form keeps its members).
+template <int S>
+struct RawDsig {
+  float dsb[S];
+};
+template <>
+struct RawDsig<1> {};
+template <bool HG, int S = 1>
+struct RawRowsT : RawDsig<S> {
   h8 xe;
   float d0, d1, d2;
   typename std::conditional<HG, uint32_t, float>::type ds;
   typename std::conditional<HG, h4, f4>::type dc;
 };
 
-template <bool ROWS, bool HG>
-__device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawRowsT<HG>& r) {
+template <bool ROWS, bool HG, int S = 1>
+__device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawRowsT<HG, S>& r) {
   r.xe = *reinterpret_cast<const h8*>(a.enc + row * a.enc_stride + g * a.enc_gstride);
   const int64_t drow = dense_row<ROWS>(a, row);
   const uint32_t ray = static_cast<uint32_t>(drow) / a.n_per_ray;
@@ -1050,14 +1159,28 @@ __device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawR
   if constexpr (HG) {
     r.ds = reinterpret_cast<const uint16_t*>(a.d_sigma_h)[drow];
     r.dc = *reinterpret_cast<const h4*>(a.d_color_h + drow * a.d_color_stride);
+  } else if constexpr (S > 1) {
+    if constexpr (S == 2) {
+      const f2 v = *reinterpret_cast<const f2*>(a.d_sigma + drow * 2);
+      r.dsb[0] = v[0];
+      r.dsb[1] = v[1];
+    } else if constexpr (S == 4) {
+      const f4 v = *reinterpret_cast<const f4*>(a.d_sigma + drow * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r.dsb[j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < S; ++j) r.dsb[j] = a.d_sigma[drow * S + j];
+    }
+    r.dc = *reinterpret_cast<const f4*>(a.d_color + drow * a.d_color_stride);
   } else {
     r.ds = a.d_sigma[drow];
     r.dc = *reinterpret_cast<const f4*>(a.d_color + drow * a.d_color_stride);
   }
 }
 
-template <bool HG>
-__device__ __forceinline__ void raw_to_rows(const RawRowsT<HG>& r, int g, Rows& in) {
+template <bool HG, int S = 1>
+__device__ __forceinline__ void raw_to_rows(const RawRowsT<HG, S>& r, int g, Rows& in) {
   in.xe = r.xe;
   in.dx = r.d0 * 2.0f - 1.0f;
   in.dy = r.d1 * 2.0f - 1.0f;
@@ -1066,6 +1189,9 @@ __device__ __forceinline__ void raw_to_rows(const RawRowsT<HG>& r, int g, Rows& 
   if constexpr (HG) {
     in.ds = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(r.ds)));
     in.dc = g == 0 ? __builtin_convertvector(r.dc, f4) : z4;
+  } else if constexpr (S > 1) {
+    in.ds = 0.0f;  // the S values go to the kernel's own registers (r.dsb)
+    in.dc = g == 0 ? r.dc : z4;
   } else {
     in.ds = r.ds;
     in.dc = g == 0 ? r.dc : z4;
@@ -1138,19 +1264,23 @@ __device__ __forceinline__ h4 tr_b(h8 x, h8 sel) {
 // HG (anr_ingp_field_bwd_ref16_rows_h, REF 2 / 3 / 4): dL/dsigma and dL/dcolor arrive as the
 // f16 values the f16 composite backward writes (10 B per row instead of 20) and are
 // converted to f32 as they are loaded; everything after the load is the f32 form's code.
-template <int W, int NHD, bool FAST, bool ROWS, bool BF, int REF = 0, bool HG = false>
+// S > 1 (build numerics, dense rows): d_sigma is (M, S); dL/dpos_out[j < S] is d_sigma[j]
+// through unit j's own ReLU (the dir network has no input from those units: zero rows in
+// its transposed first-layer fragments), all in the g == 0 lane's four registers.
+template <int W, int NHD, bool FAST, bool ROWS, bool BF, int REF = 0, bool HG = false, int S = 1>
 __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64_t tpw,
                                                      const float* wmax) {
   static_assert(!(REF && BF), "reference numerics are f16");
   static_assert(!HG || REF >= 2, "f16 gradients: the reference-numerics f16-rows forms");
-  using RawRows = RawRowsT<HG>;
+  static_assert(S == 1 || (REF == 0 && !ROWS), "S > 1: build numerics, dense rows");
+  using RawRows = RawRowsT<HG, S>;
   static_assert(REF < 3 || FAST, "the pos / list passes use the fast d_color layout");
   constexpr bool RMASK = REF >= 2;
   constexpr bool POS = REF == 4;  // no dir network in this kernel
   // MT 16-sample halves per tile, the dW contraction over NP pairs of them. (64-sample
   // tiles, MT = 4, measured 6 % slower at the same 1 wave/SIMD: profiles/r03_field_bwd_ab.log)
   constexpr int MT = 2, TR = 16 * MT, NP = MT / 2;
-  using N = Net<W, NHD>;
+  using N = Net<W, NHD, S>;
   constexpr int NT = N::NT, KB = N::KB;
   if constexpr (REF == 3) {
     // the list pass: a block none of whose waves has a listed tile leaves before its
@@ -1250,6 +1380,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   };
 
   Rows cur[MT];
+  f4 curb[S > 1 ? MT : 1];  // S > 1: dL/dsigma[row][0 .. S-1] of cur's rows
   // the next tile's raw inputs, loaded a tile ahead into alternating register sets (the
   // full-tile loop runs two tiles per trip): with one set, the loop-carried copy of the
   // prefetch registers lands wherever the register allocator puts it, and where that is
@@ -1259,7 +1390,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   if constexpr (FAST) {
     if (t_begin < t_full_end) {
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS>(a, t_begin * TR + mt * 16 + li, g, nr0[mt]);
+      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS, HG, S>(a, t_begin * TR + mt * 16 + li, g, nr0[mt]);
       // drained once, so the loop entry carries no pending loads: entered with the first
       // prefetch in flight, the waitcnt pass merges that state with the back edge's (the
       // prefetch, then the tile's d_enc stores) into a wait for everything, stores
@@ -1343,19 +1474,35 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         asm volatile("v_mov_b32 %0, %1" : "=v"(rr.d0) : "v"(nraw[mt].d0));
         asm volatile("v_mov_b32 %0, %1" : "=v"(rr.d1) : "v"(nraw[mt].d1));
         asm volatile("v_mov_b32 %0, %1" : "=v"(rr.d2) : "v"(nraw[mt].d2));
-        asm volatile("v_mov_b32 %0, %1" : "=v"(rr.ds) : "v"(nraw[mt].ds));
+        if constexpr (S == 1) {
+          asm volatile("v_mov_b32 %0, %1" : "=v"(rr.ds) : "v"(nraw[mt].ds));
+        } else {
+#pragma unroll
+          for (int j = 0; j < S; ++j)
+            asm volatile("v_mov_b32 %0, %1" : "=v"(rr.dsb[j]) : "v"(nraw[mt].dsb[j]));
+        }
         asm volatile("" : "+v"(rr.dc));
         raw_to_rows(rr, g, cur[mt]);
+        if constexpr (S > 1) {
+          curb[mt] = z4;
+#pragma unroll
+          for (int j = 0; j < S; ++j) curb[mt][j] = rr.dsb[j];
+        }
       }
       store_pend();
       const int64_t tn = tile + 1 < t_full_end ? tile + 1 : tile;
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS>(a, tn * TR + mt * 16 + li, g, nnext[mt]);
+      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS, HG, S>(a, tn * TR + mt * 16 + li, g, nnext[mt]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        load_rows<ROWS, HG>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
+        load_rows<ROWS, HG, S>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
+      if constexpr (S > 1) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          curb[mt] = load_dsig<ROWS, S>(a, tile * TR + mt * 16 + li);
+      }
     }
     const bool full = FULL;
     {
@@ -1366,9 +1513,14 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       // numerics' f32 gradients almost never are, and pay one test per tile.
       bool nz = false;
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
+      for (int mt = 0; mt < MT; ++mt) {
         nz = nz || cur[mt].ds != 0.0f || cur[mt].dc[0] != 0.0f || cur[mt].dc[1] != 0.0f ||
              cur[mt].dc[2] != 0.0f || cur[mt].dc[3] != 0.0f;
+        if constexpr (S > 1) {
+#pragma unroll
+          for (int j = 0; j < S; ++j) nz = nz || curb[mt][j] != 0.0f;
+        }
+      }
       const bool walk = __any(nz);
       if (a.tile_nz && lane == 0) a.tile_nz[tile] = walk ? 1 : 0;
       if (!walk) {
@@ -1427,16 +1579,21 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     Tile<W, NHD> t[MT];
     h4 gc[MT];
     bool dens[MT];
+    bool densb[S > 1 ? MT : 1][4];  // S > 1: the S density units' ReLU masks
     {
       bool valid[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) valid[mt] = full || tile * TR + mt * 16 + li < a.M;
       FwdWeights<W, NHD> fwl;
       fwl.load(wbt, lane, !POS && dir_walk);
-      tile_forward<W, NHD, MT, BF>(fwl, cur, valid, g, t, NoSink{}, !POS && dir_walk);
+      tile_forward<W, NHD, MT, BF, S>(fwl, cur, valid, g, t, NoSink{}, !POS && dir_walk);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         dens[mt] = (REF ? r16(t[mt].po[0]) : t[mt].po[0]) > 0.0f;
+        if constexpr (S > 1) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) densb[mt][j] = t[mt].po[j] > 0.0f;
+        }
         f4 gv;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -1547,9 +1704,18 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   #pragma unroll
             for (int i = 0; i < 4; ++i) acc[mt][i] = r16(r16(r16(acc[mt][i]) * inv_s) * s);
           }
-          // pos_out[:, 0] is the density: its gradient is dL/dsigma through the ReLU
-          const float dsv = dens[mt] ? cur[mt].ds * s : 0.0f;
-          acc[mt][0] = g == 0 ? dsv : acc[mt][0];
+          if constexpr (S == 1) {
+            // pos_out[:, 0] is the density: its gradient is dL/dsigma through the ReLU
+            const float dsv = dens[mt] ? cur[mt].ds * s : 0.0f;
+            acc[mt][0] = g == 0 ? dsv : acc[mt][0];
+          } else {
+            // pos_out[:, j < S]: band j's density, dL/dsigma[j] through its own ReLU
+#pragma unroll
+            for (int j = 0; j < S; ++j) {
+              const float dsv = densb[mt][j] ? curb[mt][j] * s : 0.0f;
+              acc[mt][j] = g == 0 ? dsv : acc[mt][j];
+            }
+          }
           dpo[mt] = to_h4<BF>(acc[mt]);
         }
       }
@@ -1712,7 +1878,15 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
-      if constexpr (!POS) flush(rdir + N::D0, 32, dD0[nt * 2 + kt], 16 * nt, dir_col(16 * kt + li));
+      if constexpr (!POS) {
+        if constexpr (S == 1) {
+          flush(rdir + N::D0, 32, dD0[nt * 2 + kt], 16 * nt, dir_col<1>(16 * kt + li));
+        } else {
+          // a padding slot's sum goes to its padding column, or nowhere (S = 4: no column)
+          const int c = dir_col<S>(16 * kt + li);
+          if (c >= 0) flush(rdir + N::D0, N::LD0, dD0[nt * 2 + kt], 16 * nt, c);
+        }
+      }
       flush(rpos + N::P0, 32, dP0[nt * 2 + kt], 16 * nt, 16 * kt + li);
     }
   __syncthreads();
@@ -1746,10 +1920,11 @@ static BwdGeom tile_geom(int64_t M, int per_cu) {
 }
 // every backward form of one d_color layout (fast or general) runs the grid of its plain
 // (REF 0, f32-gradient) instantiation
-template <int W, int NHD, bool BF>
+template <int W, int NHD, bool BF, int S = 1>
 static BwdGeom bwd_geom(int64_t M, bool fast) {
-  const void* fn = fast ? reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, BF>)
-                        : reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, false, false, BF>);
+  const void* fn =
+      fast ? reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>)
+           : reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>);
   return tile_geom(M, blocks_per_cu(fn, 256));
 }
 
@@ -1766,14 +1941,14 @@ static int64_t list_blocks() {
   return 256LL * blocks_per_cu(fn, 256);
 }
 
-template <int W, int NHD, bool BF>
+template <int W, int NHD, bool BF, int S = 1>
 static int64_t bwd_workspace(int64_t M) {
   if (BF || M <= 0) return 0;
   // the larger wave count of the fast and general d_color layouts, so a workspace sized
   // once serves whichever runs
   int64_t n = 0;
   for (int f = 0; f < 2; ++f) {
-    const int64_t w = bwd_geom<W, NHD, BF>(M, f == 1).nw;
+    const int64_t w = bwd_geom<W, NHD, BF, S>(M, f == 1).nw;
     n = w > n ? w : n;
   }
   return static_cast<int64_t>(sizeof(float)) * n;
@@ -1897,15 +2072,81 @@ static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t s
   return 0;
 }
 
+// S > 1 density outputs: the f32 dense-row forward (both forms), the density kernel and
+// the build-numerics backward; same grids and launch rules as run(), from the S kernels' own
+// occupancy. The callers refuse every other form before they get here.
+template <int W, int NHD, bool BF, int S>
+static int run_s(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
+  static_assert(S >= 2 && S <= 4, "run(): S = 1");
+  using N = Net<W, NHD, S>;
+  const int waves = 4;
+  if (a.rows || a.color_h || a.d_color_h || a.loss_scale > 0.0f) return 1;
+  if (op == 1) {
+    const int64_t tiles = (a.M + 15) / 16;
+    const void* fn =
+        reinterpret_cast<const void*>(&fwd_kernel<W, NHD, false, BF, false, false, S>);
+    const int64_t blocks =
+        persistent_blocks((tiles + waves - 1) / waves, blocks_per_cu(fn, 64 * waves));
+    // S <= 4 <= color_stride: the sigma byte offsets stay below the colour rows' bound
+    const bool ut = g_fwd_ut && a.n_per_ray % 16 == 0 && a.n_out == 4 &&
+                    (a.color_stride & 3) == 0 && a.M * a.color_stride * 4 < (int64_t{1} << 31);
+    if (ut)
+      hipLaunchKernelGGL((fwd_kernel<W, NHD, false, BF, true, false, S>), dim3(blocks),
+                         dim3(64 * waves), 0, st, a);
+    else
+      hipLaunchKernelGGL((fwd_kernel<W, NHD, false, BF, false, false, S>), dim3(blocks),
+                         dim3(64 * waves), 0, st, a);
+    return 0;
+  }
+  if (op == 3) {
+    const int64_t tiles = (a.M + 15) / 16;
+    const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, 8);
+    hipLaunchKernelGGL((density_kernel<W, NHD, BF, S>), dim3(blocks), dim3(64 * waves), 0, st, a);
+    return 0;
+  }
+  const bool fast = a.n_out == 4 && (a.d_color_stride & 3) == 0 && a.d_sigma != nullptr;
+  const size_t lds = static_cast<size_t>(N::n_packed) * 2 + sizeof(float) * (N::NPOS + N::NDIR);
+  if (lds > 160 * 1024) return 1;
+  const BwdGeom gm = bwd_geom<W, NHD, BF, S>(a.M, fast);
+  if (!BF && (ws == nullptr || ws_bytes < static_cast<int64_t>(sizeof(float)) * gm.nw))
+    return 2;
+  const float target = ldexpf(1.0f, g_target_log2);
+  const dim3 grid(static_cast<unsigned>(gm.blocks)), block(64 * waves);
+  if (!BF)
+    hipLaunchKernelGGL((absmax_kernel<false, S>), dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32,
+                       ws);
+  if (fast)
+    hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>), grid, block, 0, st,
+                       a, target, gm.tpw, ws);
+  else
+    hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>), grid, block, 0, st,
+                       a, target, gm.tpw, ws);
+  return 0;
+}
+
 template <int W, int NHD>
-static void launch_pack(const float* pp, const float* pd, _Float16* out, bool bf, hipStream_t st) {
+static void launch_pack(const float* pp, const float* pd, _Float16* out, bool bf, int ns,
+                        hipStream_t st) {
   using N = Net<W, NHD>;
   const dim3 grid((N::n_packed + 255) / 256);
-  if (bf)
-    hipLaunchKernelGGL((pack_kernel<W, NHD, true>), grid, dim3(256), 0, st, pp, pd, out);
-  else
-    hipLaunchKernelGGL((pack_kernel<W, NHD, false>), grid, dim3(256), 0, st, pp, pd, out);
+#define ANR_PACK(BFV, SV) \
+  hipLaunchKernelGGL((pack_kernel<W, NHD, BFV, SV>), grid, dim3(256), 0, st, pp, pd, out)
+  switch (ns * 2 + (bf ? 1 : 0)) {
+    case 2: ANR_PACK(false, 1); break;
+    case 3: ANR_PACK(true, 1); break;
+    case 4: ANR_PACK(false, 2); break;
+    case 5: ANR_PACK(true, 2); break;
+    case 6: ANR_PACK(false, 3); break;
+    case 7: ANR_PACK(true, 3); break;
+    case 8: ANR_PACK(false, 4); break;
+    case 9: ANR_PACK(true, 4); break;
+  }
+#undef ANR_PACK
 }
+
+// Density outputs S of a dir network: its 20 - S inputs are SH2 (4) and pos_out[S:16]
+// (multi_band_extinction: S = num_bands; 1 otherwise). Meaningful once variant() != 0.
+static int n_sigma(const anr_mlp_desc* dir) { return 20 - dir->n_input; }
 
 // (W, NHD) of a supported pos/dir pair, or 0
 static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
@@ -1914,7 +2155,8 @@ static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
       pos->n_output_padded != 16 || pos->n_hidden_layers != 1 ||
       pos->output_activation != ANR_ACT_NONE)
     return 0;
-  if (dir->n_input != 19 || dir->n_input_padded != 32 || dir->n_output < 1 || dir->n_output > 16 ||
+  if (dir->n_input < 16 || dir->n_input > 19 ||
+      dir->n_input_padded != (dir->n_input + 15) / 16 * 16 || dir->n_output < 1 || dir->n_output > 16 ||
       dir->n_output_padded != 16 || dir->width != pos->width ||
       (dir->n_hidden_layers != 1 && dir->n_hidden_layers != 2))
     return 0;
@@ -1961,10 +2203,43 @@ static int dispatch_t(int v, int op, const Args& a, float* ws, int64_t ws_bytes,
   }
   return 1;
 }
-static int dispatch(int v, bool bf, int op, const Args& a, float* ws, int64_t ws_bytes,
+template <bool BF, int S>
+static int dispatch_s(int v, int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
+  switch (v) {
+    case 321: return run_s<32, 1, BF, S>(op, a, ws, ws_bytes, st);
+    case 322: return run_s<32, 2, BF, S>(op, a, ws, ws_bytes, st);
+    case 641: return run_s<64, 1, BF, S>(op, a, ws, ws_bytes, st);
+    case 642: return run_s<64, 2, BF, S>(op, a, ws, ws_bytes, st);
+  }
+  return 1;
+}
+// ns: the pair's density outputs (n_sigma)
+static int dispatch(int v, int ns, bool bf, int op, const Args& a, float* ws, int64_t ws_bytes,
                     hipStream_t st) {
-  return bf ? dispatch_t<true>(v, op, a, ws, ws_bytes, st)
-            : dispatch_t<false>(v, op, a, ws, ws_bytes, st);
+  switch (ns) {
+    case 1:
+      return bf ? dispatch_t<true>(v, op, a, ws, ws_bytes, st)
+                : dispatch_t<false>(v, op, a, ws, ws_bytes, st);
+    case 2:
+      return bf ? dispatch_s<true, 2>(v, op, a, ws, ws_bytes, st)
+                : dispatch_s<false, 2>(v, op, a, ws, ws_bytes, st);
+    case 3:
+      return bf ? dispatch_s<true, 3>(v, op, a, ws, ws_bytes, st)
+                : dispatch_s<false, 3>(v, op, a, ws, ws_bytes, st);
+    case 4:
+      return bf ? dispatch_s<true, 4>(v, op, a, ws, ws_bytes, st)
+                : dispatch_s<false, 4>(v, op, a, ws, ws_bytes, st);
+  }
+  return 1;
+}
+// Entry points that stay at one density output answer a multi-band pair with this.
+static bool multi_band(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
+  return variant(pos, dir) != 0 && n_sigma(dir) > 1;
+}
+static int refuse_bands(const char* entry) {
+  ::anr::set_error("%s: unsupported for a dir network with more than one density output "
+                   "(multi_band_extinction): anr_ingp_field_fwd / _density / _bwd take it", entry);
+  return ANR_E_UNSUPPORTED;
 }
 
 }  // namespace field
@@ -1990,12 +2265,23 @@ extern "C" int64_t anr_ingp_field_bwd_workspace_bytes(const anr_mlp_desc* pos,
                                                       const anr_mlp_desc* dir,
                                                       int32_t mma_dtype, int64_t M) {
   if (mma_dtype == ANR_BF16) return 0;
-  switch (variant(pos, dir)) {
-    case 321: return bwd_workspace<32, 1, false>(M);
-    case 322: return bwd_workspace<32, 2, false>(M);
-    case 641: return bwd_workspace<64, 1, false>(M);
-    case 642: return bwd_workspace<64, 2, false>(M);
+  const int v = variant(pos, dir);
+  if (v == 0) return 0;
+#define ANR_WS(SV)                                            \
+  switch (v) {                                                \
+    case 321: return bwd_workspace<32, 1, false, SV>(M);      \
+    case 322: return bwd_workspace<32, 2, false, SV>(M);      \
+    case 641: return bwd_workspace<64, 1, false, SV>(M);      \
+    case 642: return bwd_workspace<64, 2, false, SV>(M);      \
+  }                                                           \
+  return 0
+  switch (n_sigma(dir)) {
+    case 1: ANR_WS(1);
+    case 2: ANR_WS(2);
+    case 3: ANR_WS(3);
+    case 4: ANR_WS(4);
   }
+#undef ANR_WS
   return 0;
 }
 
@@ -2041,10 +2327,10 @@ extern "C" int anr_ingp_field_pack(const anr_mlp_desc* pos, const anr_mlp_desc* 
   _Float16* out = static_cast<_Float16*>(packed);
   const bool bf = mma_dtype == ANR_BF16;
   switch (v) {
-    case 321: launch_pack<32, 1>(pos_params, dir_params, out, bf, st); break;
-    case 322: launch_pack<32, 2>(pos_params, dir_params, out, bf, st); break;
-    case 641: launch_pack<64, 1>(pos_params, dir_params, out, bf, st); break;
-    case 642: launch_pack<64, 2>(pos_params, dir_params, out, bf, st); break;
+    case 321: launch_pack<32, 1>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
+    case 322: launch_pack<32, 2>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
+    case 641: launch_pack<64, 1>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
+    case 642: launch_pack<64, 2>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
   }
   ANR_CHECK_LAUNCH("anr_ingp_field_pack");
   return ANR_OK;
@@ -2060,7 +2346,14 @@ static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_fwd: mma_dtype must be ANR_F16 or ANR_BF16");
   ANR_CHECK_ARG(M >= 0 && M < (1LL << 31), "anr_ingp_field_fwd: bad M");
   if (M == 0) return ANR_OK;
+  const int ns = n_sigma(dir);
+  if (ns > 1 && (half_out || rows))
+    return refuse_bands(half_out ? "anr_ingp_field_fwd_h" : "anr_ingp_field_fwd_rows");
   ANR_CHECK_ARG(packed && enc && dirs && sigma && color, "anr_ingp_field_fwd: null pointer");
+  // S > 1: a row's S densities leave as one store
+  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
+                "anr_ingp_field_fwd: sigma (M, %d) must be %d-byte aligned", ns,
+                ns == 3 ? 4 : 4 * ns);
   ANR_CHECK_ARG(n_per_ray >= 1 && n_per_ray < (1LL << 31) && color_stride >= dir->n_output,
                 "anr_ingp_field_fwd: bad shape/stride");
   ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(enc) & 15) == 0 &&
@@ -2088,7 +2381,7 @@ static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   }
   a.color_stride = color_stride;
   a.rows = rows;
-  ANR_CHECK_ARG(dispatch(v, mma_dtype == ANR_BF16, 1, a, nullptr, 0,
+  ANR_CHECK_ARG(dispatch(v, ns, mma_dtype == ANR_BF16, 1, a, nullptr, 0,
                          reinterpret_cast<hipStream_t>(stream)) == 0,
                 "anr_ingp_field_fwd: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_field_fwd");
@@ -2104,6 +2397,7 @@ extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const floa
                                       anr_stream_t stream) {
   const int v = variant(pos, dir);
   if (M == 0) return ANR_OK;
+  if (v != 0 && n_sigma(dir) > 1) return refuse_bands("anr_ingp_hash_field_fwd");
   ANR_CHECK_ARG(grid && x && table && planes && packed && dirs && sigma && color,
                 "anr_ingp_hash_field_fwd: null pointer");
   if (v == 0 || !mma_ok(mma_dtype) || table_dtype != ANR_F16 || grid->n_dims != 3 ||
@@ -2170,8 +2464,14 @@ static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_bwd: mma_dtype must be ANR_F16 or ANR_BF16");
   ANR_CHECK_ARG(M >= 0 && M < (1LL << 31), "anr_ingp_field_bwd: bad M");
   if (M == 0) return ANR_OK;
+  const int ns = n_sigma(dir);
+  if (ns > 1 && (loss_scale > 0.0f || rows))
+    return refuse_bands(rows ? "anr_ingp_field_bwd_rows" : "anr_ingp_field_bwd_ref16");
   ANR_CHECK_ARG(packed && enc && dirs && d_color && (d_enc || (d_enc_h && row_nz)) && g_pos && g_dir,
                 "anr_ingp_field_bwd: null pointer");
+  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(d_sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
+                "anr_ingp_field_bwd: d_sigma (M, %d) must be %d-byte aligned", ns,
+                ns == 3 ? 4 : 4 * ns);
   ANR_CHECK_ARG(d_enc_h == nullptr || loss_scale > 0.0f,
                 "anr_ingp_field_bwd: f16 rows and row bits are reference numerics only");
   ANR_CHECK_ARG(n_per_ray >= 1 && n_per_ray < (1LL << 31) && d_color_stride >= dir->n_output &&
@@ -2215,7 +2515,7 @@ static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
     a.tile_count = static_cast<uint32_t*>(tiles_ws);
     a.tile_list = reinterpret_cast<int32_t*>(static_cast<char*>(tiles_ws) + 256);
   }
-  const int rc = dispatch(v, mma_dtype == ANR_BF16, 2, a, static_cast<float*>(workspace),
+  const int rc = dispatch(v, ns, mma_dtype == ANR_BF16, 2, a, static_cast<float*>(workspace),
                           workspace_bytes, reinterpret_cast<hipStream_t>(stream));
   ANR_CHECK_ARG(rc != 2,
                 "anr_ingp_field_bwd: workspace missing or smaller than "
@@ -2253,7 +2553,10 @@ extern "C" int anr_ingp_field_density(const anr_mlp_desc* pos, const anr_mlp_des
   ANR_CHECK_ARG(M >= 0 && M < (1LL << 31), "anr_ingp_field_density: bad M");
   if (M == 0) return ANR_OK;
   ANR_CHECK_ARG(packed && enc && sigma, "anr_ingp_field_density: null pointer");
-
+  const int ns = n_sigma(dir);
+  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
+                "anr_ingp_field_density: sigma (M, %d) must be %d-byte aligned", ns,
+                ns == 3 ? 4 : 4 * ns);
   ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(enc) & 15) == 0 &&
                     (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
                 "anr_ingp_field_density: enc/packed must be 16-byte aligned");
@@ -2262,7 +2565,7 @@ extern "C" int anr_ingp_field_density(const anr_mlp_desc* pos, const anr_mlp_des
   ANR_CHECK_ARG(set_enc(a, enc, enc_stride, M), "anr_ingp_field_density: bad enc_stride");
   a.M = M;
   a.sigma = sigma;
-  ANR_CHECK_ARG(dispatch(v, mma_dtype == ANR_BF16, 3, a, nullptr, 0,
+  ANR_CHECK_ARG(dispatch(v, ns, mma_dtype == ANR_BF16, 3, a, nullptr, 0,
                          reinterpret_cast<hipStream_t>(stream)) == 0,
                 "anr_ingp_field_density: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_field_density");
@@ -2288,6 +2591,7 @@ extern "C" int anr_ingp_field_bwd_ref16(const anr_mlp_desc* pos, const anr_mlp_d
                                         int64_t d_color_stride, float* d_enc,
                                         int64_t d_enc_stride, float* g_pos, float* g_dir,
                                         float loss_scale, anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16: loss_scale must be > 0");
   return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
                    d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, nullptr,
@@ -2302,6 +2606,7 @@ extern "C" int anr_ingp_field_bwd_ref16_tiles(const anr_mlp_desc* pos, const anr
                                               float* d_enc, int64_t d_enc_stride, float* g_pos,
                                               float* g_dir, float loss_scale, uint8_t* tile_nz,
                                               anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_tiles");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_tiles: loss_scale must be > 0");
   ANR_CHECK_ARG(tile_nz != nullptr, "anr_ingp_field_bwd_ref16_tiles: null tile_nz");
   return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
@@ -2322,6 +2627,7 @@ extern "C" int anr_ingp_field_bwd_ref16_rows(const anr_mlp_desc* pos, const anr_
                                              float* g_dir, float loss_scale, uint32_t* row_nz,
                                              void* workspace, int64_t workspace_bytes,
                                              anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_rows");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_rows: loss_scale must be > 0");
   ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr,
                 "anr_ingp_field_bwd_ref16_rows: null d_enc / row_nz");
@@ -2345,6 +2651,7 @@ extern "C" int anr_ingp_field_bwd_ref16_rows_h(const anr_mlp_desc* pos, const an
                                                float* g_dir, float loss_scale, uint32_t* row_nz,
                                                void* workspace, int64_t workspace_bytes,
                                                anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_rows_h");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_rows_h: loss_scale must be > 0");
   ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr,
                 "anr_ingp_field_bwd_ref16_rows_h: null d_enc / row_nz");
@@ -2365,6 +2672,7 @@ extern "C" int anr_ingp_field_fwd_rows(const anr_mlp_desc* pos, const anr_mlp_de
                                        int64_t M, const int32_t* rows, float* sigma,
                                        float* color, int64_t color_stride,
                                        anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_fwd_rows");
   ANR_CHECK_ARG(rows || M == 0, "anr_ingp_field_fwd_rows: null rows");
   return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, rows,
                    sigma, color, color_stride, stream);
@@ -2378,6 +2686,7 @@ extern "C" int anr_ingp_field_bwd_rows(const anr_mlp_desc* pos, const anr_mlp_de
                                        float* d_enc, int64_t d_enc_stride, float* g_pos,
                                        float* g_dir, void* workspace, int64_t workspace_bytes,
                                        anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_rows");
   ANR_CHECK_ARG(rows || M == 0, "anr_ingp_field_bwd_rows: null rows");
   return field_bwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, rows,
                    d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir,

@@ -30,6 +30,10 @@ extern "C" {
 #endif
 
 /* Added to ABI 5 without a version change (additive; every ABI 5 call behaves as it did):
+ * multi-band extinction in the fused field -- dir descriptors of 16..18 inputs (S = 20 -
+ * n_input = 2..4 density outputs), refused before, are accepted by anr_ingp_field_supported
+ * / _packed_size / _pack / _fwd / _density / _bwd / _bwd_workspace_bytes, with sigma and
+ * d_sigma (M, S); no signature changes (see "K6 + K7 fused" below);
  * the include_height input -- 4-D hash grids (anr_hashgrid_init_nd; forward, backward and
  * planes take its descriptors), anr_prep_params.mode 2 in anr_sample_uniform_bins ((B,N,4)
  * coords), anr_append_heights and anr_append_heights_f64.
@@ -343,8 +347,21 @@ int anr_ingp_dir_mlp_bwd(const anr_mlp_desc* d, int32_t precision, const void* p
  * K6 + K7 fused: the Instant-NGP radiance field after the hash encoding, one kernel each
  * way (replaces pos_mlp -> dir_encoder -> dir_mlp -> relu at instant_ngp.py:163-184).
  * ------------------------------------------------------------------------------------
- * Supported pairs: pos 32 -> W -> 16 (1 hidden layer, no output activation), dir 19 -> W
- * (1 or 2 hidden layers) -> n_output <= 16, W in {32, 64}.
+ * Supported pairs: pos 32 -> W -> 16 (1 hidden layer, no output activation), dir (20 - S)
+ * -> W (1 or 2 hidden layers) -> n_output <= 16, W in {32, 64}, S in {1, 2, 3, 4}.
+ * S is the number of density outputs and is read from the dir descriptor, S = 20 -
+ * dir.n_input: the dir network's inputs are SH2(dir) (4) and pos_out[:, S:16]
+ * (instant_ngp.py:64-77). S = 1 is the reference's default; S = num_bands with
+ * multi_band_extinction (instant_ngp.py:46-48,178,184). dir.n_input_padded must be tcnn's
+ * (n_input + 15) / 16 * 16: 32 for S <= 3, 16 for S = 4, so the first dir layer's parameter
+ * rows are 32 or 16 wide and anr_mlp_n_params(dir) differs accordingly; the packed size
+ * does not depend on S.
+ * With S > 1, sigma and d_sigma are (M, S) row-major f32, contiguous (row m at element
+ * m * S), sigma[m][j] = relu(pos_out[m][j]); the pointers must be aligned to 4 S bytes
+ * (4 bytes for S = 3). anr_ingp_field_fwd, anr_ingp_field_density, anr_ingp_field_bwd and
+ * its workspace query take S > 1; anr_ingp_field_fwd_h, anr_ingp_field_fwd_rows / _bwd_rows,
+ * anr_ingp_hash_field_fwd and every anr_ingp_field_bwd_ref16* entry stay at S = 1 and
+ * return ANR_E_UNSUPPORTED for S > 1 (M = 0 still returns ANR_OK).
  * mma_dtype: ANR_F16 (the reference's tcnn precision: f16 operands, f32 accumulation) or
  * ANR_BF16 (BASELINE configs[4], beyond the reference: bf16 operands over the same f16
  * hash features, f32 accumulation; no gradient scaling). Pack, forward and backward of one
@@ -356,8 +373,9 @@ int anr_ingp_dir_mlp_bwd(const anr_mlp_desc* d, int32_t precision, const void* p
  *   the row layout (M, enc_stride) with 16-byte aligned rows, or enc_stride = -P for the
  *   level-quad planes of anr_hashgrid_fwd_planes (P >= 8 M, multiple of 8).
  * Forward: enc, dirs (M/n_per_ray, 3) f32 ->
- *   sigma (M,) f32 = relu(pos_out[:,0]), color (M, n_output) f32 = relu(dir_mlp(...)).
- * Backward: d_sigma (M,) f32 (nullable), d_color (M, n_output) f32 -> d_enc (M, 32) f32
+ *   sigma (M,) f32 = relu(pos_out[:,0]) ((M, S) = relu(pos_out[:, :S]) for S > 1),
+ *   color (M, n_output) f32 = relu(dir_mlp(...)).
+ * Backward: d_sigma (M,) f32 ((M, S) for S > 1; nullable), d_color (M, n_output) f32 -> d_enc (M, 32) f32
  *   WRITTEN; g_pos / g_dir f32 parameter gradients ACCUMULATED. `workspace` is caller-
  *   owned device memory of at least anr_ingp_field_bwd_workspace_bytes(pos, dir,
  *   mma_dtype, M) bytes (per-wavefront f16 gradient maxima; 0 bytes for bf16, then it may
@@ -404,7 +422,7 @@ int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const float* x, int64
                             const anr_mlp_desc* dir, int32_t mma_dtype, const void* packed,
                             const float* dirs, int64_t n_per_ray, float* sigma, float* color,
                             int64_t color_stride, anr_stream_t stream);
-/* Density only: sigma[r] = relu(pos_mlp(enc[r])[0]) (f32), bit-identical to
+/* Density only: sigma[r] = relu(pos_mlp(enc[r])[0]) (f32; (M, S) for S > 1), bit-identical to
  * anr_ingp_field_fwd's sigma, without the dir MLP -- the extract loop
  * (scripts/extract.py:203-209 -> instant_ngp.py:208-247 reads only the extinction) and the
  * occupancy grid. Same descriptors and packed weights as anr_ingp_field_fwd. */

@@ -373,10 +373,10 @@ __device__ __forceinline__ h8 enc_in(h8 e) {
 // (two instructions per pair; written as asm because the compiler expands it to compares
 // and selects). The result feeds MFMAs, and hipcc pads nothing for a VALU write inside an
 // asm statement: the two wait states a VALU-written MFMA operand needs end the string.
-template <bool BF>
-__device__ __forceinline__ h4 mask_h4(f4 g, h4 act) {
+// mask_bits takes g in the 16-bit operand type, mask_h4 converts it first.
+__device__ __forceinline__ h4 mask_bits(h4 g, h4 act) {
   typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-  const u2 gb = __builtin_bit_cast(u2, to_h4<BF>(g)), ab = __builtin_bit_cast(u2, act);
+  const u2 gb = __builtin_bit_cast(u2, g), ab = __builtin_bit_cast(u2, act);
   uint32_t m0, m1;
   asm("v_pk_min_u16 %0, %2, 1 op_sel_hi:[1,0]\n\t"
       "v_pk_min_u16 %1, %3, 1 op_sel_hi:[1,0]\n\t"
@@ -386,6 +386,44 @@ __device__ __forceinline__ h4 mask_h4(f4 g, h4 act) {
       : "=&v"(m0), "=&v"(m1)
       : "v"(ab.x), "v"(ab.y), "v"(gb.x), "v"(gb.y));
   return __builtin_bit_cast(h4, u2{m0, m1});
+}
+template <bool BF>
+__device__ __forceinline__ h4 mask_h4(f4 g, h4 act) {
+  return mask_bits(to_h4<BF>(g), act);
+}
+// Rank-1 pieces of the pos pass (f16). d2 holds two f16 scalars, HALF picks one.
+// w * d: one f16 multiply per value (v_pk_mul_f16 with the scalar's half broadcast by
+// op_sel), denormals kept, the exact product rounded once.
+template <int HALF>
+__device__ __forceinline__ h4 scale_h4(h4 w, uint32_t d2) {
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  const u2 wb = __builtin_bit_cast(u2, w);
+  uint32_t p0, p1;
+  if constexpr (HALF == 0) {
+    asm("v_pk_mul_f16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(p0) : "v"(wb.x), "v"(d2));
+    asm("v_pk_mul_f16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(p1) : "v"(wb.y), "v"(d2));
+  } else {
+    asm("v_pk_mul_f16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(p0) : "v"(wb.x), "v"(d2));
+    asm("v_pk_mul_f16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(p1) : "v"(wb.y), "v"(d2));
+  }
+  return __builtin_bit_cast(h4, u2{p0, p1});
+}
+// acc[i] += x[i] * d in f32 (v_fma_mix_f32 reads the f16 halves as they are: the product is
+// exact, the sum rounded once)
+template <int HALF>
+__device__ __forceinline__ void fma_h4(float (&acc)[4], h4 x, uint32_t d2) {
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  const u2 xb = __builtin_bit_cast(u2, x);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if constexpr (HALF == 0) {
+      asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * j]) : "v"(xb[j]), "v"(d2));
+      asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * j + 1]) : "v"(xb[j]), "v"(d2));
+    } else {
+      asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * j]) : "v"(xb[j]), "v"(d2));
+      asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,1,0]" : "+v"(acc[2 * j + 1]) : "v"(xb[j]), "v"(d2));
+    }
+  }
 }
 
 // Reference numerics: the gradient tiles hold tcnn's loss-scaled f16 values, many of them
@@ -1179,6 +1217,14 @@ __device__ __forceinline__ void load_raw(const Args& a, int64_t row, int g, RawR
   }
 }
 
+// the OR of a raw f16 dL/dcolor row's bits (the f32 form has no use for it)
+__device__ __forceinline__ uint32_t or_bits(h4 v) {
+  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+  const u2 b = __builtin_bit_cast(u2, v);
+  return b.x | b.y;
+}
+__device__ __forceinline__ uint32_t or_bits(f4) { return 0u; }
+
 template <bool HG, int S = 1>
 __device__ __forceinline__ void raw_to_rows(const RawRowsT<HG, S>& r, int g, Rows& in) {
   in.xe = r.xe;
@@ -1259,7 +1305,11 @@ __device__ __forceinline__ h4 tr_b(h8 x, h8 sel) {
 // tiles whose dL/dcolor is zero in every row -- the pos network only, so the dir network's
 // registers, dW accumulators and LDS sums are not part of the kernel and more waves fit a
 // SIMD -- while a tile with a nonzero dL/dcolor is appended to a.tile_list (a.tile_count)
-// and left alone. REF 3 (the list pass, launched after it): REF 2 on exactly the listed
+// and left alone. Its output layer is rank 1 (see w1r in the kernel), its dL/denc rows stay
+// f16 from the accumulator to the store, and its zero tests read the f16 bits: the pass is
+// bound by VALU issue (profiles/pos_rank1_summary.md); same dL/denc, row bits and list as
+// REF 2, g_pos up to the f32 order of row 0 of dW_P1.
+// REF 3 (the list pass, launched after it): REF 2 on exactly the listed
 // tiles (count read on the device), the whole network.
 // HG (anr_ingp_field_bwd_ref16_rows_h, REF 2 / 3 / 4): dL/dsigma and dL/dcolor arrive as the
 // f16 values the f16 composite backward writes (10 B per row instead of 20) and are
@@ -1316,6 +1366,24 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     o1 = tr_b<BF>(x, tc.sel[1]);
   };
   constexpr int R0 = 0, R1 = 16;
+  // POS: dL/dpos_out is dL/dsigma in unit 0 and exact zeros in the other 15 units, so the
+  // output layer's backward is rank 1: dhp = P1[0][:] * dpo0 (one f16 product per value,
+  // what the MFMA's single nonzero term rounded to f16 is) and only row 0 of dW_P1 gets
+  // sums. Row 0 of P1 for this lane's units 16 kt + 4 g + i stays in registers (k = 0 of
+  // the transposed fragment: lane 4 g + i, element 0), row 0 of dW_P1 is summed per lane
+  // in f32 over the lane's samples and reduced over the 16 sample lanes after the loop.
+  h4 w1r[NT];
+  float dP1r[NT][4];
+  if constexpr (POS) {
+#pragma unroll
+    for (int kt = 0; kt < NT; ++kt) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        w1r[kt][i] = wsm[N::oBP1 + kt * N::F16 + 16 * g + 4 * i];
+        dP1r[kt][i] = 0.0f;
+      }
+    }
+  }
 
   const int64_t n_tiles = (a.M + TR - 1) / TR;
   const int64_t w_id = static_cast<int64_t>(blockIdx.x) * waves + wave;
@@ -1410,6 +1478,16 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) pend[kt][mt] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+  // POS: the deferred rows as the f16 values that are stored (pend unused), scaled back by
+  // one packed f16 multiply where 1 / loss_scale is an f16 number (any power of two in
+  // range): f16(acc) * inv_s is then exact in f32 either way and rounded to f16 once
+  h4 pendh[2][MT];
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) pendh[kt][mt] = h4{0, 0, 0, 0};
+  const _Float16 inv_h = static_cast<_Float16>(inv_s);
+  const bool inv_is_h = static_cast<float>(inv_h) == inv_s;
   // one lane's 4 values of dL/denc row `row`, columns 16 kt + 4 g .. + 3
   auto put = [&](int64_t row, int kt, const f4& v) {
     if constexpr (RMASK) {
@@ -1440,6 +1518,21 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
            v1[1] != 0.0f || v1[2] != 0.0f || v1[3] != 0.0f;
   };
   auto store_pend = [&]() {
+    if constexpr (POS) {
+      typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+      bool nz[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        _Float16* const p = a.d_enc_h + (pend_tile * TR + mt * 16 + li) * a.d_enc_stride + 4 * g;
+        *reinterpret_cast<h4*>(p) = pendh[0][mt];
+        *reinterpret_cast<h4*>(p + 16) = pendh[1][mt];
+        // any of the 8 values nonzero (-0 is zero): the bits without the signs
+        const u2 b0 = __builtin_bit_cast(u2, pendh[0][mt]), b1 = __builtin_bit_cast(u2, pendh[1][mt]);
+        nz[mt] = ((b0.x | b0.y | b1.x | b1.y) & 0x7FFF7FFFu) != 0u;
+      }
+      put_mask(pend_tile, nz);
+      return;
+    }
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -1458,6 +1551,10 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       asm volatile("" : "+v"(zoff));
       wbt = wsm + zoff;
     }
+    // POS, f16 gradients, full tiles: "any dL/dcolor nonzero" from the raw bits of the row's
+    // four f16 values (every lane group loaded the same four), not from eight f32 compares
+    constexpr bool RAWC = POS && HG && FAST && FULL;
+    uint32_t dcor = 0;
     if constexpr (FAST && FULL) {
       // the tile's head: this tile's prefetched inputs are converted here (hoisted into the
       // previous tile, the conversion waits on loads just issued) and the next tile's loads
@@ -1482,6 +1579,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
             asm volatile("v_mov_b32 %0, %1" : "=v"(rr.dsb[j]) : "v"(nraw[mt].dsb[j]));
         }
         asm volatile("" : "+v"(rr.dc));
+        if constexpr (RAWC) dcor |= or_bits(rr.dc);
         raw_to_rows(rr, g, cur[mt]);
         if constexpr (S > 1) {
           curb[mt] = z4;
@@ -1511,11 +1609,13 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       // the backward (wave-uniform). Under the reference numerics tcnn's x128 f16 backward
       // leaves most tiles so once training settles (profiles/r05_state160.log); the build
       // numerics' f32 gradients almost never are, and pay one test per tile.
-      bool nz = false;
+      bool nz = RAWC && (dcor & 0x7FFF7FFFu) != 0u;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        nz = nz || cur[mt].ds != 0.0f || cur[mt].dc[0] != 0.0f || cur[mt].dc[1] != 0.0f ||
-             cur[mt].dc[2] != 0.0f || cur[mt].dc[3] != 0.0f;
+        nz = nz || cur[mt].ds != 0.0f;
+        if constexpr (!RAWC)
+          nz = nz || cur[mt].dc[0] != 0.0f || cur[mt].dc[1] != 0.0f || cur[mt].dc[2] != 0.0f ||
+               cur[mt].dc[3] != 0.0f;
         if constexpr (S > 1) {
 #pragma unroll
           for (int j = 0; j < S; ++j) nz = nz || curb[mt][j] != 0.0f;
@@ -1529,7 +1629,10 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt) pend[kt][mt] = zero4;
+            for (int mt = 0; mt < MT; ++mt) {
+              pend[kt][mt] = zero4;
+              pendh[kt][mt] = h4{0, 0, 0, 0};
+            }
           pend_tile = tile;
           return;
         }
@@ -1561,7 +1664,9 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     // in the general-layout kernel the branch's register copies read dW accumulators right
     // behind their inline-asm MFMAs (tools/mfma_hazards.py)
     bool dir_walk = true;
-    if constexpr (REF && FAST) {
+    if constexpr (RAWC) {
+      dir_walk = __any((dcor & 0x7FFF7FFFu) != 0u);
+    } else if constexpr (REF && FAST) {
       bool cnz = false;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -1719,7 +1824,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
           dpo[mt] = to_h4<BF>(acc[mt]);
         }
       }
-    } else {
+    } else if constexpr (!POS) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         f4 acc = z4;
@@ -1729,7 +1834,26 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     }
     // ---- pos output layer: dW_P1 (16 x W) += dpo^T · X_ph ; dhp = P1^T dpo
     h4 dhp[MT][NT];
-    {
+    if constexpr (POS) {
+      // rank 1 (see w1r): dpo0 = f16(dL/dsigma * scale) through the density ReLU, formed in
+      // the row's g == 0 lane (the one holding pos_out[0]) and handed to its other three
+      // lane groups, both halves of the tile in one 32-bit word
+      uint32_t pk = 0;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const _Float16 d = static_cast<_Float16>(g == 0 && dens[mt] ? cur[mt].ds * s : 0.0f);
+        pk |= static_cast<uint32_t>(__builtin_bit_cast(uint16_t, d)) << (16 * mt);
+      }
+      pk = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(li << 2, static_cast<int>(pk)));
+      static_assert(MT == 2, "dpo0 of the tile's two halves in one word");
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt) {
+        dhp[0][kt] = mask_bits(scale_h4<0>(w1r[kt], pk), t[0].hp[kt]);
+        dhp[1][kt] = mask_bits(scale_h4<1>(w1r[kt], pk), t[1].hp[kt]);
+        fma_h4<0>(dP1r[kt], t[0].hp[kt], pk);
+        fma_h4<1>(dP1r[kt], t[1].hp[kt], pk);
+      }
+    } else {
       h4 wp1[NT];
 #pragma unroll
       for (int kt = 0; kt < NT; ++kt) wp1[kt] = bfrag16(N::oBP1 + kt * N::F16);
@@ -1785,6 +1909,19 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const int64_t row = tile * TR + mt * 16 + li;
+          if constexpr (POS && FAST && FULL) {
+            // the stored f16 values directly (see pendh)
+            h4 hv = to_h4<false>(acc[mt]);
+            if (inv_is_h) {
+              hv = hv * h4{inv_h, inv_h, inv_h, inv_h};
+            } else {
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+                hv[i] = static_cast<_Float16>(static_cast<float>(hv[i]) * inv_s);
+            }
+            pendh[kt][mt] = hv;
+            continue;
+          }
           f4 v = acc[mt] * inv_s;
           if constexpr (REF) {
 #pragma unroll
@@ -1814,8 +1951,8 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       agpr_pin(dD2);
       agpr_pin(dD1);
       agpr_pin(dD0);
+      agpr_pin(dP1);
     }
-    agpr_pin(dP1);
     agpr_pin(dP0);
   };
   if constexpr (REF == 3) {
@@ -1849,8 +1986,8 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     agpr_pin(dD2);
     agpr_pin(dD1);
     agpr_pin(dD0);
+    agpr_pin(dP1);
   }
-  agpr_pin(dP1);
   agpr_pin(dP0);
   // dW flush: each wavefront's partials (unscaled by its own gradient scale) go into the
   // block's LDS sums, then the block adds them to the f32 gradients with one coalesced
@@ -1865,8 +2002,20 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   };
 #pragma unroll
   for (int kt = 0; kt < NT; ++kt) {
-    if constexpr (!POS) flush(rdir + N::D2, W, dD2[kt], 0, 16 * kt + li);
-    flush(rpos + N::P1, W, dP1[kt], 0, 16 * kt + li);
+    if constexpr (!POS) {
+      flush(rdir + N::D2, W, dD2[kt], 0, 16 * kt + li);
+      flush(rpos + N::P1, W, dP1[kt], 0, 16 * kt + li);
+    } else {
+      // row 0 of dW_P1: the lane's sums over its samples, added over the 16 sample lanes of
+      // its group (the four groups hold different units); lane li == 0 adds the total
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float v = dP1r[kt][i];
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
+        if (li == 0 && v != 0.0f) atomicAdd(rpos + N::P1 + 16 * kt + 4 * g + i, v * inv_s);
+      }
+    }
   }
   if constexpr (NHD == 2 && !POS) {
 #pragma unroll

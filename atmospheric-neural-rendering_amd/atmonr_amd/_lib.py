@@ -324,6 +324,7 @@ _SIGNATURES = {
     "anr_loss_ref16_fwd_bwd": (
         c_int32, [c_int32, _P, c_int32, _P, _P, c_int64, c_float, _P, _P, _P, _P]),
     "anr_grad_quantize_f16": (c_int32, [_P, c_int64, c_float, _P]),
+    "anr_grad_quantize_add_f16": (c_int32, [_P, _P, c_int64, c_float, _P]),
     "anr_ingp_field_bwd_ref16": (
         c_int32,
         [POINTER(MlpDesc), POINTER(MlpDesc), _P, _P, c_int64, _P, c_int64, c_int64, _P, _P,

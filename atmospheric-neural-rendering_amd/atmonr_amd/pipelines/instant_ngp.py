@@ -12,7 +12,12 @@ Two execution paths, identical semantics:
   gradients between kernels, the composite on K8 with z scaled in-kernel, the loss on K9.
 * ``fused=False``: the reference's op-by-op graph (sample_uniform_bins, the point
   preprocessor, the (p+1)/2 remap, tcnn-style modules with f16 outputs) on the same
-  kernels — used to check that the fused path changes nothing but speed.
+  kernels — used to check that the fused path changes nothing but speed. In reference
+  numerics it is a second, independent implementation of the fused reference path: the
+  six modules carry ``loss_scale = 128`` (atmonr_amd.tcnn: tinycudann's loss-scaled f16
+  backward and its f16 parameter gradient, rounded per module call), the cat of the f32
+  directions with the f16 ``pos_out[:, 1:]`` promotes to f32 as in the reference, and the
+  composite and the loss are the same f16 kernels the fused path uses.
 
 Two numerics (``numerics=`` or the config key ``"numerics"``):
 
@@ -23,7 +28,8 @@ Two numerics (``numerics=`` or the config key ``"numerics"``):
   28-76, instant_ngp.py:259-263; csrc/ref16.hip), tinycudann's loss-scaled (x128) f16
   module backward with f16 gradients at the module boundaries, and tcnn's f16 parameter
   gradients (tinycudann/modules.py). Opt-in, for PSNR parity with the reference; f16
-  networks, fused field, no occupancy culling.
+  networks, no occupancy culling; the fused field, or with ``fused=False`` the module
+  graph above.
 
 ``include_height: true`` (needs ``point_preprocessor: null``, as the base class asserts):
 the position grid is 4-D and every sample's normalised ellipsoidal height is its fourth
@@ -108,10 +114,13 @@ class InstantNGPPipeline(Pipeline):
         self.mlp_dtype = mlp_dtype
         # tinycudann's loss scale for f16 modules (reference numerics only)
         self.loss_scale = 128.0 if numerics == "reference" else None
-        if numerics == "reference" and not (fused and dtype == torch.float16 and
+        if numerics == "reference" and self.num_density_outputs != 1:
+            raise ValueError("numerics='reference' does not take multi_band_extinction (the "
+                             "f16 composite has one density channel)")
+        if numerics == "reference" and not (dtype == torch.float16 and
                                             mlp_dtype == torch.float16 and occupancy is None):
-            raise ValueError("numerics='reference' runs the fused f16 field (f16 modules, "
-                             "no occupancy culling)")
+            raise ValueError("numerics='reference' runs f16 modules (the fused f16 field, or "
+                             "fused=False: the module graph) without occupancy culling")
         # reference numerics: rays whose f16 alpha rounded to exactly 1 (their gradients are
         # zero, not torch's zero-input cumprod branch; ref16.hip), counted over the
         # pipeline's life (zero_rays_total; the Trainer warns when it grows)
@@ -120,14 +129,16 @@ class InstantNGPPipeline(Pipeline):
         self.surface_stream = os.environ.get("ANR_SURFACE_STREAM", "1") != "0"
         ingp = self.config["instant_ngp"]
         nb = self.config["num_bands"]
+        # the unfused reference path: every module runs tinycudann's backward itself
+        mls = self.loss_scale if not fused else None
         self.pos_encoder = Encoding(4 if self.include_height else 3, ingp["encoding"], seed=seed,
-                                    dtype=dtype)
+                                    dtype=dtype, loss_scale=mls)
         self.pos_mlp = Network(self.pos_encoder.n_output_dims, 16, ingp["network"],
-                               seed=seed + 1, dtype=mlp_dtype)
+                               seed=seed + 1, dtype=mlp_dtype, loss_scale=mls)
         self.dir_encoder = Encoding(3 + 16 - self.num_density_outputs, ingp["dir_encoding"],
-                                    seed=seed + 2, dtype=dtype)
+                                    seed=seed + 2, dtype=dtype, loss_scale=mls)
         self.dir_mlp = Network(self.dir_encoder.n_output_dims, nb, ingp["rgb_network"],
-                               seed=seed + 3, dtype=mlp_dtype)
+                               seed=seed + 3, dtype=mlp_dtype, loss_scale=mls)
         if self.fused and self.num_density_outputs != 1 and not field_fused(self):
             # the native field refuses the pair (its widths / depths): the op-by-op path
             if mlp_dtype == torch.bfloat16:
@@ -139,10 +150,18 @@ class InstantNGPPipeline(Pipeline):
         # field's sigma / colour and their gradients (field.py, ANR_REF_F16_IO)
         fdt = torch.float32 if fused and numerics == "build" else None
         self.surf_encoder = Encoding(2 + 3, ingp["surface_encoding"], seed=seed + 4,
-                                     dtype=dtype, output_dtype=fdt)
+                                     dtype=dtype, output_dtype=fdt, loss_scale=mls)
         self.surf_mlp = Network(self.surf_encoder.n_output_dims, nb, ingp["surface_network"],
-                                seed=seed + 5, dtype=dtype, output_dtype=fdt)
-        self.surf_mlp.loss_scale = self.loss_scale
+                                seed=seed + 5, dtype=dtype, output_dtype=fdt, loss_scale=mls)
+        # the modules' backward arithmetic is the pipeline's choice alone, whatever default
+        # atmonr_amd.tcnn.reference_numerics() has set for bare modules
+        for m in self.modules():
+            m.loss_scale = mls
+        if fused and numerics == "reference":
+            # fused reference numerics: the surface network runs the scaled backward into
+            # .grad, and _TcnnGradsAtBackwardEnd (or the optimizer) rounds every gradient
+            self.surf_mlp.loss_scale = self.loss_scale
+            self.surf_mlp._round_per_call = False
         d = self.dir_mlp.desc
         self._dir_desc_relu = _lib.mlp_desc(d.n_input, d.n_output, d.width, d.n_hidden_layers,
                                             True)
@@ -179,10 +198,11 @@ class InstantNGPPipeline(Pipeline):
         the bench shape). The update is the same; ``param.grad`` between backward and the
         step then holds the unrounded f32 sums, so code that reads or reduces gradients in
         between (all-reduce, clipping, parity tests) must not defer. No-op in build
-        numerics."""
+        numerics, and with ``fused=False``: there each module has rounded its gradient per
+        call (as tinycudann does) before it reaches ``param.grad``."""
         from ..optim import FusedAdam
 
-        if self.numerics != "reference":
+        if self.numerics != "reference" or not self.fused:
             return
         if not isinstance(optimizer, FusedAdam) or not optimizer.multi_tensor:
             raise ValueError("defer_grad_quantize needs a FusedAdam(multi_tensor=True)")
@@ -330,8 +350,17 @@ class InstantNGPPipeline(Pipeline):
         sigma = pos_out[..., : self.num_density_outputs].view(B_, N, -1)
         color = F.relu(color)
         sigma = F.relu(sigma)
-        color_map, _, weights, atmo, surf = render_with_surface(
-            z_vals * (self.scale / 1000), color, sigma, color_surf)
+        if self.numerics == "reference":
+            if self._zero_rays is None:
+                self._zero_rays = torch.zeros(1, dtype=torch.int32, device=color.device)
+            # f16 colour / density / surface colour (the modules' outputs) into the f16
+            # composite; z_vals * (scale / 1000) is formed in f32 by the kernel
+            color_map, _, weights, atmo, surf = render_with_surface_ref16(
+                z_vals, color, sigma, color_surf, z_scale=self.scale / 1000,
+                zero_rays=self._zero_rays, need_alpha=False)
+        else:
+            color_map, _, weights, atmo, surf = render_with_surface(
+                z_vals * (self.scale / 1000), color, sigma, color_surf)
         results = {
             "color_fine": color[:, :-1],
             "color_surf": color_surf,

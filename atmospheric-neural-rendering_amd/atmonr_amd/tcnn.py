@@ -15,6 +15,30 @@ Parameter per module (float32 master copy, as tcnn's torch bindings keep it) and
 ``dtype`` follows tcnn: float16 by default (tables, weights and outputs in f16, f32
 accumulation); pass ``dtype=torch.float32`` for the exact-f32 kernels used by the 1e-4
 parity tests.
+
+``loss_scale`` (constructor argument and attribute of both classes, as tinycudann's modules
+have it) selects the backward's arithmetic:
+
+* ``None`` (default): this build's backward -- f32 gradients between kernels, a
+  per-wavefront power-of-two scale inside the f16 MLP backward, parameter gradients
+  accumulated in f32 straight into ``params.grad``.
+* a positive number (tinycudann: 128 for f16 modules): tinycudann's loss-scaled f16
+  backward, PER MODULE CALL (tinycudann/modules.py, restated in oracle/ref_ingp.py
+  ``_TcnnCall``): the incoming f16 gradient becomes ``f16(f32(g) * s)`` (``|g * s| >=
+  65520`` is +-inf, not clamped), the call's parameter gradient is ``f16(f16(sum at scale)
+  / s)`` handed to autograd as f32, and the input gradient is ``f16(at scale) / s`` in the
+  input's dtype (f16 for a network fed f16, f32 for an encoding). A module used twice in
+  one graph rounds each call's gradient separately: the call's sums are scattered into a
+  zeroed f32 scratch of the module's (allocated at the first such backward, the size of
+  ``params``) and anr_grad_quantize_add_f16 rounds them, adds them to ``params.grad`` (or
+  to a fresh buffer handed to autograd when there is none yet) and leaves the scratch
+  zeroed. f16 modules with f16 outputs only. The hash grid scatters the unscaled rows:
+  for a power-of-two ``s`` the f32 sum times ``s`` is the sum of the scaled rows.
+
+``reference_numerics()`` makes 128 the default ``loss_scale`` of f16 modules constructed
+afterwards (f32 modules keep ``None``: tinycudann scales those by 1), so that the
+reference's own ``tcnn.Encoding(...)`` / ``tcnn.Network(...)`` lines give tinycudann's
+arithmetic unchanged.
 """
 
 from __future__ import annotations
@@ -28,6 +52,56 @@ from torch import nn
 
 from . import _lib
 from ._lib import ANRError, call, dtype_code, ptr
+
+
+# default loss_scale of f16 modules whose constructor is given none (reference_numerics)
+_default_loss_scale: float | None = None
+TCNN_LOSS_SCALE = 128.0  # tinycudann.modules: default loss scale of f16 parameters
+
+
+def reference_numerics(enabled: bool = True) -> None:
+    """Modules constructed from now on default to tinycudann's backward arithmetic
+    (``loss_scale = 128`` for f16 modules with f16 outputs; f32 modules keep ``None``).
+    ``reference_numerics(False)`` restores the build's default. Existing modules, and the
+    forward of every module, are unchanged."""
+    global _default_loss_scale
+    _default_loss_scale = TCNN_LOSS_SCALE if enabled else None
+
+
+def _resolve_loss_scale(loss_scale, dtype, output_dtype, what: str) -> float | None:
+    f16 = dtype == torch.float16 and output_dtype == torch.float16
+    if loss_scale is None:
+        return _default_loss_scale if f16 else None
+    s = float(loss_scale)
+    if not (s > 0.0 and math.isfinite(s)):
+        raise ANRError(f"{what}: loss_scale={loss_scale!r} must be a positive number or None")
+    if not f16:
+        raise ANRError(f"{what}: loss_scale={loss_scale!r} is tinycudann's f16 backward and "
+                       f"needs dtype=float16 with f16 outputs (dtype={dtype}, "
+                       f"output_dtype={output_dtype}); f32 modules take loss_scale=None")
+    return s
+
+
+def _call_grad(mod, scratch: torch.Tensor, dev):
+    """Round one call's parameter-gradient sums (``scratch``) as tinycudann does and add them
+    to ``mod.params.grad``; returns what the autograd Function hands back for ``params``:
+    None when the kernel added into an existing f32 ``.grad``, else the fresh buffer."""
+    grad, direct = _lib.grad_target(mod.params, dev)
+    call("anr_grad_quantize_add_f16", ptr(scratch), ptr(grad), scratch.numel(),
+         float(mod.loss_scale), _lib.stream(dev), tag="grad_quantize_add")
+    if direct:
+        _lib.grad_done(mod.params)
+        return None
+    return grad
+
+
+def _grad_scratch(mod, dev) -> torch.Tensor:
+    """The module's zeroed f32 scatter buffer on ``dev`` (every user leaves it zeroed)."""
+    sc = mod.__dict__.get("_grad_scratch")
+    if sc is None or sc.device != dev or sc.numel() != mod.params.numel():
+        sc = torch.zeros(mod.params.numel(), device=dev, dtype=torch.float32)
+        mod.__dict__["_grad_scratch"] = sc
+    return sc
 
 
 def _lower(d: dict) -> dict:
@@ -178,6 +252,8 @@ class _EncodingFn(torch.autograd.Function):
         x, p = ctx.saved_tensors
         enc: Encoding = ctx.enc
         dout = dout.contiguous()
+        if enc.loss_scale:
+            return _EncodingFn._backward_tcnn(ctx, x, p, enc, dout)
         s = _lib.stream(x.device)
         need_x = ctx.needs_input_grad[0]
         need_p = ctx.needs_input_grad[1]
@@ -199,18 +275,56 @@ class _EncodingFn(torch.autograd.Function):
             dx = dx.to(x.dtype)
         return dx, None if direct else dparams, None
 
+    @staticmethod
+    def _backward_tcnn(ctx, x, p, enc: "Encoding", dout):
+        """tinycudann's loss-scaled backward of one call (module docstring)."""
+        ls = float(enc.loss_scale)
+        s = _lib.stream(x.device)
+        need_x = ctx.needs_input_grad[0]
+        need_p = ctx.needs_input_grad[1] and enc.params.numel() > 0
+        # parameters: the hash grids scatter the f16 rows, unscaled, into the zeroed scratch
+        # (x s is exact in f32), rounded and added to the gradient below
+        scratch = _grad_scratch(enc, x.device) if need_p else None
+        # inputs: the leaves' backward on the scaled f16 rows f16(f32(g) * s) (inf past
+        # f16's range, as tinycudann's), rounded to f16 at scale, then / s. (An inf under a
+        # SphericalHarmonics column makes that row's direction gradient nan: 0 * inf in
+        # the constant band.)
+        has_dx = need_x and any(not isinstance(leaf, _HashGrid) for _, leaf in enc._leaves)
+        dx = torch.zeros(x.shape, device=x.device, dtype=torch.float32) if need_x else None
+        dout_s = (dout.float() * ls).to(torch.float16) if has_dx else None
+        col_out = 0
+        for (col_in, leaf), poff in zip(enc._leaves, enc._param_offsets):
+            xs = x[:, col_in:col_in + leaf.n_in]
+            if isinstance(leaf, _HashGrid):
+                if scratch is not None:
+                    leaf.bwd(xs, p[poff:poff + leaf.n_params], dout, col_out,
+                             scratch[poff:poff + leaf.n_params], None, s)
+            elif has_dx:
+                leaf.bwd(xs, None, dout_s, col_out, None, dx[:, col_in:col_in + leaf.n_in], s)
+            col_out += leaf.n_out
+        gp = _call_grad(enc, scratch, x.device) if need_p else None
+        if has_dx:
+            dx = dx.to(torch.float16).float() / ls
+        if dx is not None:
+            dx = dx.to(x.dtype)
+        return dx, gp, None
+
 
 class Encoding(nn.Module):
-    """tinycudann.Encoding(n_input_dims, encoding_config, seed=1337, dtype=None)."""
+    """tinycudann.Encoding(n_input_dims, encoding_config, seed=1337, dtype=None).
+    ``loss_scale``: module docstring."""
 
     def __init__(self, n_input_dims: int, encoding_config: dict, seed: int = 1337,
-                 dtype: torch.dtype | None = None, output_dtype: torch.dtype | None = None):
+                 dtype: torch.dtype | None = None, output_dtype: torch.dtype | None = None,
+                 loss_scale: float | None = None):
         super().__init__()
         self.n_input_dims = n_input_dims
         self.encoding_config = encoding_config
         self.dtype = torch.float16 if dtype is None else dtype
         # extension: outputs (and therefore their gradients) may be kept in f32
         self.output_dtype = self.dtype if output_dtype is None else output_dtype
+        self.loss_scale = _resolve_loss_scale(loss_scale, self.dtype, self.output_dtype,
+                                              "Encoding")
         self._leaves = _build(n_input_dims, encoding_config)
         self.n_output_dims = sum(leaf.n_out for _, leaf in self._leaves)
         self._param_offsets = []
@@ -261,7 +375,12 @@ class _NetworkFn(torch.autograd.Function):
         net: Network = ctx.net
         dout = dout.contiguous()
         prec = _net_prec(net)
-        dparams, direct = _lib.grad_target(net.params, x.device)
+        # tcnn's arithmetic rounds the gradient per call: its sums go to the module's scratch
+        per_call = bool(net.loss_scale) and net._round_per_call
+        if per_call:
+            dparams, direct = _grad_scratch(net, x.device), False
+        else:
+            dparams, direct = _lib.grad_target(net.params, x.device)
         din = None
         if ctx.needs_input_grad[0]:
             din = torch.empty(x.shape, device=x.device, dtype=x.dtype)
@@ -281,6 +400,8 @@ class _NetworkFn(torch.autograd.Function):
                  dtype_code(dout.dtype), dout.stride(0), ptr(din), dtype_code(x.dtype),
                  x.stride(0) if din is not None else 0, ptr(dparams), ptr(ws), ws_bytes,
                  _lib.stream(x.device))
+        if per_call:
+            return din, _call_grad(net, dparams, x.device), None
         if direct:
             _lib.grad_done(net.params)
         return din, None if direct else dparams, None
@@ -298,11 +419,12 @@ def _net_prec(net) -> int:
 
 
 class Network(nn.Module):
-    """tinycudann.Network(n_input_dims, n_output_dims, network_config, seed=1337)."""
+    """tinycudann.Network(n_input_dims, n_output_dims, network_config, seed=1337).
+    ``loss_scale``: module docstring."""
 
     def __init__(self, n_input_dims: int, n_output_dims: int, network_config: dict,
                  seed: int = 1337, dtype: torch.dtype | None = None,
-                 output_dtype: torch.dtype | None = None):
+                 output_dtype: torch.dtype | None = None, loss_scale: float | None = None):
         super().__init__()
         cfg = _lower(network_config)
         otype = str(cfg.get("otype", "FullyFusedMLP")).lower()
@@ -319,8 +441,13 @@ class Network(nn.Module):
         self.dtype = torch.float16 if dtype is None else dtype
         self.output_dtype = self.dtype if output_dtype is None else output_dtype
         # None: the kernels' own per-wavefront f16 gradient scaling; a number (tcnn: 128):
-        # tinycudann's fixed loss scale and its f16 input gradient (reference numerics)
-        self.loss_scale: float | None = None
+        # tinycudann's fixed loss scale, its f16 input gradient and its per-call f16
+        # parameter gradient (module docstring)
+        self.loss_scale: float | None = _resolve_loss_scale(loss_scale, self.dtype,
+                                                            self.output_dtype, "Network")
+        # False: the owner rounds the accumulated gradient itself (the fused reference
+        # pipeline: once at the end of backward, or inside its optimizer)
+        self._round_per_call = True
         self.width = int(cfg.get("n_neurons", 64))
         self.n_hidden_layers = int(cfg.get("n_hidden_layers", 2))
         self.desc = _lib.mlp_desc(n_input_dims, n_output_dims, self.width, self.n_hidden_layers,
@@ -370,5 +497,6 @@ def batch_size_granularity() -> int:
     return 1
 
 
-__all__ = ["Encoding", "Network", "free_temporary_memory", "batch_size_granularity"]
+__all__ = ["Encoding", "Network", "reference_numerics", "free_temporary_memory",
+           "batch_size_granularity"]
 _ = Any

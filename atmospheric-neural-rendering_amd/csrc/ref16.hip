@@ -711,6 +711,51 @@ __global__ void __launch_bounds__(256) quantize_kernel(float* __restrict__ g, in
     g[i] = h(h(g[i] * s) * inv_s);
 }
 
+// One module call's gradient, rounded as quantize_kernel rounds it and added to grad:
+// grad[i] += f16(f16(scratch[i] * s) / s), scratch[i] = 0 (the module's scatter buffer, left
+// zeroed for its next call). grad + head is 16-byte aligned (head < 4 elements; grad may be
+// a view at any element offset of a flat gradient bucket): the body runs in 16-byte vectors
+// of grad -- and of scratch where scratch + head is aligned too (SVEC) -- and the up to 3
+// elements before and the up to 3 after it go one to a thread of the first block.
+typedef float f4v __attribute__((ext_vector_type(4)));
+template <bool SVEC>
+__global__ void __launch_bounds__(256) quantize_add_kernel(float* __restrict__ scratch,
+                                                           float* __restrict__ grad, int64_t n,
+                                                           int head, float s, float inv_s) {
+  const int64_t nvec = (n - head) / 4;
+  const int64_t tid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  float* sb = scratch + head;
+  float* gb = grad + head;
+  for (int64_t i = tid; i < nvec; i += stride) {
+    f4v g = *reinterpret_cast<const f4v*>(gb + 4 * i);
+    f4v v;
+    if (SVEC) {
+      v = *reinterpret_cast<const f4v*>(sb + 4 * i);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = sb[4 * i + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[k] = g[k] + h(h(v[k] * s) * inv_s);
+    *reinterpret_cast<f4v*>(gb + 4 * i) = g;
+    if (SVEC) {
+      *reinterpret_cast<f4v*>(sb + 4 * i) = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sb[4 * i + k] = 0.0f;
+    }
+  }
+  const int64_t tail0 = head + 4 * nvec;  // first element after the body
+  int64_t e = -1;
+  if (tid < head) e = tid;
+  else if (tid - head < n - tail0) e = tail0 + (tid - head);
+  if (e >= 0) {
+    grad[e] = grad[e] + h(h(scratch[e] * s) * inv_s);
+    scratch[e] = 0.0f;
+  }
+}
+
 // Rays per wavefront: 2 from 8,192 rays up, 1 below (fewer rays leave SIMDs idle, and
 // then one ray per wave's extra waves beat the shared scans); anr_composite_ref16_set_rays
 // (1 / 2 / 4 / 8) overrides (r04 sweep in DESIGN.md §10). Halved until the band-sum lanes
@@ -915,5 +960,34 @@ extern "C" int anr_grad_quantize_f16(float* grad, int64_t n, float loss_scale,
   hipLaunchKernelGGL(ref16::quantize_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0,
                      as_stream(stream), grad, n, loss_scale, 1.0f / loss_scale);
   ANR_CHECK_LAUNCH("anr_grad_quantize_f16");
+  return ANR_OK;
+}
+
+extern "C" int anr_grad_quantize_add_f16(float* scratch, float* grad, int64_t n,
+                                         float loss_scale, anr_stream_t stream) {
+  ANR_CHECK_ARG((scratch != nullptr && grad != nullptr) || n == 0,
+                "anr_grad_quantize_add_f16: null argument");
+  ANR_CHECK_ARG(n >= 0 && loss_scale > 0.0f, "anr_grad_quantize_add_f16: bad argument");
+  if (n == 0) return ANR_OK;
+  const uintptr_t sp = reinterpret_cast<uintptr_t>(scratch), gp = reinterpret_cast<uintptr_t>(grad);
+  ANR_CHECK_ARG((sp & 3) == 0 && (gp & 3) == 0,
+                "anr_grad_quantize_add_f16: pointers must be 4-byte aligned");
+  ANR_CHECK_ARG(sp + 4 * static_cast<uintptr_t>(n) <= gp || gp + 4 * static_cast<uintptr_t>(n) <= sp,
+                "anr_grad_quantize_add_f16: scratch and grad overlap");
+  int64_t head = static_cast<int64_t>(((16 - (gp & 15)) & 15) / 4);  // elements before grad aligns
+  if (head > n) head = n;
+  const bool svec = ((sp + 4 * static_cast<uintptr_t>(head)) & 15) == 0;
+  int64_t blocks = ceil_div((n - head) / 4, 256);
+  if (blocks > 8192) blocks = 8192;
+  if (blocks < 1) blocks = 1;  // the head and tail elements alone
+  if (svec)
+    hipLaunchKernelGGL(ref16::quantize_add_kernel<true>, dim3(static_cast<unsigned>(blocks)),
+                       dim3(256), 0, as_stream(stream), scratch, grad, n,
+                       static_cast<int>(head), loss_scale, 1.0f / loss_scale);
+  else
+    hipLaunchKernelGGL(ref16::quantize_add_kernel<false>, dim3(static_cast<unsigned>(blocks)),
+                       dim3(256), 0, as_stream(stream), scratch, grad, n,
+                       static_cast<int>(head), loss_scale, 1.0f / loss_scale);
+  ANR_CHECK_LAUNCH("anr_grad_quantize_add_f16");
   return ANR_OK;
 }

@@ -37,12 +37,15 @@ extern "C" {
  * the include_height input -- 4-D hash grids (anr_hashgrid_init_nd; forward, backward and
  * planes take its descriptors), anr_prep_params.mode 2 in anr_sample_uniform_bins ((B,N,4)
  * coords), anr_append_heights and anr_append_heights_f64.
- * ABI 5 (r06): anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and its workspace size;
+ * ABI 5 (r06): the row-bit hash-grid backward and the f16-row field backward with its pos /
+ * list-pass workspace -- anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and
+ * anr_ingp_field_bwd_ref16_rows_workspace_bytes;
  * added since without a version change (additive): anr_ingp_field_fwd_h,
  * anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16 interchange between the
  * field and the f16 composite); anr_composite_ref16_fwd_park and
  * anr_composite_ref16_bwd_parked (the forward parks T, exp and the surface product for its
- * backward, which then skips its replay of the forward).
+ * backward, which then skips its replay of the forward); anr_grad_quantize_add_f16 (the
+ * per-call f16 rounding of a tcnn module's parameter gradient, added to the caller's).
  * ABI 4 (r06): anr_ingp_hash_field_fwd. ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused
  * field entry points' enc_stride < 0
  * selecting the level-quad-plane layout it writes. */
@@ -668,6 +671,15 @@ int anr_loss_ref16_fwd_bwd(int32_t loss_type, const void* color_map, int32_t C,
 /* tcnn's parameter gradient of an f16 module at loss scale s: g <- f16(f16(g*s)/s), in
  * place over n f32 values (the value tinycudann/modules.py hands to torch). */
 int anr_grad_quantize_f16(float* grad, int64_t n, float loss_scale, anr_stream_t stream);
+/* One module call's parameter gradient, rounded the same way and added to the caller's
+ * gradient: grad[i] += f16(f16(scratch[i]*s)/s), then scratch[i] = 0, over n f32 values
+ * (tinycudann rounds per module call, so a call's sums are scattered into a zeroed scratch
+ * of the module's, which this leaves zeroed for the next call). scratch and grad are any
+ * two 4-byte-aligned, non-overlapping ranges (grad may be a view at any offset of a flat
+ * bucket); n == 0 is accepted. Equal bit for bit to anr_grad_quantize_f16 on scratch
+ * followed by grad += scratch. */
+int anr_grad_quantize_add_f16(float* scratch, float* grad, int64_t n, float loss_scale,
+                              anr_stream_t stream);
 /* The fused field backward (anr_ingp_field_bwd) with tcnn's backward semantics: fixed
  * f16 gradient scale loss_scale (128), ReLU masks on the f16 outputs, and the
  * module-boundary gradients of the reference (dir_mlp -> dir_encoder -> pos_out, pos_mlp

@@ -10,6 +10,7 @@
 // One HBM pass: reads p, g, m, v; writes p, m, v, optionally the f16 shadow of p used by
 // the next forward, and optionally zeroes g (optimizer.zero_grad fused in).
 // anr_adam_step_multi updates every tensor of a step in one launch (FusedAdam's default).
+// 1-beta is 1.0f - (f32 beta); torch's is 1 - beta in double: exp_avg_sq ~1.2e-6 off.
 
 #pragma clang fp contract(off)
 

@@ -30,6 +30,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ANR_HIP_LIB", os.path.join(_HERE, "_native", "libanr_hip.so"))
 
 F32, F16, BF16 = 0, 1, 2
+RENDER_BUILD, RENDER_REFERENCE = 0, 1  # anr_ingp_render's numerics argument
 MAX_LEVELS = 32
 
 LOSS_CODES = {
@@ -259,6 +260,11 @@ _SIGNATURES = {
         c_int32,
         [POINTER(HashGridDesc), _P, c_int64, _P, c_int32, _P, c_int64, POINTER(MlpDesc),
          POINTER(MlpDesc), c_int32, _P, _P, c_int64, _P, _P, c_int64, _P],
+    ),
+    "anr_ingp_render": (
+        c_int32,
+        [POINTER(HashGridDesc), _P, _P, _P, c_int64, c_int64, _P, c_int32, POINTER(MlpDesc),
+         POINTER(MlpDesc), c_int32, _P, _P, c_float, c_int32, _P, _P, _P, _P],
     ),
     "anr_ingp_field_density": (
         c_int32,

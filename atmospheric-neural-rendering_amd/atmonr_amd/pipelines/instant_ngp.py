@@ -51,6 +51,7 @@ kernels do not see the grid's dimension.
 
 from __future__ import annotations
 
+import ctypes
 import os
 from itertools import chain
 from typing import Any, Mapping
@@ -69,6 +70,12 @@ from ..samplers import (points_with_heights, preprocess_points, sample_and_prepr
                         sample_uniform_bins)
 from ..tcnn import Encoding, Network
 from .pipeline import Pipeline
+
+
+# InstantNGPPipeline.render(fused="auto") takes anr_ingp_render where it serves (measured at
+# the workload shape: DESIGN §5, profiles/render_fused.json); ANR_RENDER_FUSED=0 keeps
+# "auto" on forward's path (A/B), fused=True still runs the kernel
+_RENDER_AUTO = os.environ.get("ANR_RENDER_FUSED", "1") != "0"
 
 
 class InstantNGPPipeline(Pipeline):
@@ -277,14 +284,15 @@ class InstantNGPPipeline(Pipeline):
             return out
         return join
 
-    def _forward_fused(self, ray_batch, u=None):
+    def _forward_fused(self, ray_batch, u=None, random=True):
         B = ray_batch["origin"].shape[0]
         N = self.config["num_samples_per_ray"]
         # the per-ray surface branch (6 small kernels each way) is enqueued first, on its
         # own stream, so it runs beside the sampler / hash grid forward and, in backward,
         # beside the hash-grid backward
         surf_branch = self._surface_async(ray_batch)
-        _, z_vals, coords = sample_and_preprocess(ray_batch, N, self._prep_ngp, u=u)
+        _, z_vals, coords = sample_and_preprocess(ray_batch, N, self._prep_ngp, random=random,
+                                                  u=u)
         occ = self.occupancy
         if occ is not None and self.training:
             occ.update(pipeline_density(self))
@@ -329,11 +337,11 @@ class InstantNGPPipeline(Pipeline):
             results["norm_heights_fine"] = coords[..., 3]
         return results
 
-    def _forward_reference(self, ray_batch, u=None):
+    def _forward_reference(self, ray_batch, u=None, random=True):
         # instant_ngp.py:137-206, op for op
         B_ = ray_batch["origin"].shape[0]
         N = self.config["num_samples_per_ray"]
-        pts, z_vals = sample_uniform_bins(ray_batch, N, u=u)
+        pts, z_vals = sample_uniform_bins(ray_batch, N, random=random, u=u)
         if self.point_preprocessor:
             pts = self.point_preprocessor(pts)
         pts = (pts + 1) / 2
@@ -374,6 +382,97 @@ class InstantNGPPipeline(Pipeline):
         if self.include_height:
             results["norm_heights_fine"] = pts[..., 3]
         return results
+
+    # ------------------------------------------------------------------ render
+    _RENDER_KEYS = ("color_map_fine", "color_map_atmo", "color_map_surf", "z_vals_fine")
+
+    def render_kernel_refusal(self, n_samples: int | None = None) -> str | None:
+        """Why anr_ingp_render cannot serve this pipeline (None: it can): it takes the
+        fused f16 / bf16 field over a 3-D f16 hash grid of 16 levels x 2 features, one
+        density, four colour bands, no active occupancy grid, and a sample count that is a
+        multiple of 64."""
+        N = self.config["num_samples_per_ray"] if n_samples is None else n_samples
+        if not field_fused(self):
+            return "the field does not run the fused f16 / bf16 kernels (fused=False or f32 MLPs)"
+        if self.pos_encoder.dtype != torch.float16:
+            return "the hash table is not f16"
+        if self.num_density_outputs != 1:
+            return "multi_band_extinction (more than one density output)"
+        if self.include_height:
+            return "include_height (a 4-D hash grid)"
+        if self.occupancy is not None and self.occupancy.active:
+            return "an active occupancy grid"
+        if N < 64 or N % 64:
+            return f"{N} samples per ray (a positive multiple of 64 is needed)"
+        d = self.pos_encoder.hash_grids[0].desc
+        if (d.n_dims, d.n_levels, d.n_features) != (3, 16, 2) or self.dir_mlp.n_output_dims != 4:
+            return "a hash grid other than 3-D 16 levels x 2 features, or other than 4 bands"
+        return None
+
+    def render(self, ray_batch: Mapping[str, torch.Tensor], u: torch.Tensor | None = None,
+               random: bool = False, fused: bool | str = "auto") -> dict[str, torch.Tensor]:
+        """Colour maps of a batch of rays without a backward: ``color_map_fine``,
+        ``color_map_atmo``, ``color_map_surf`` (B, num_bands) and ``z_vals_fine`` (B, N).
+        Always under ``torch.no_grad()``. The samples sit at the bin midpoints
+        (``random=False``, samplers.py:37-41: a render is deterministic), at ``u`` (B, N)
+        where given, or at fresh draws with ``random=True``. No side effect: no ``.grad`` is
+        touched, the occupancy grid is not updated, nothing is parked for a backward,
+        ``zero_rays_total`` does not move, ``training`` stays as it is.
+
+        ``fused="auto"``: where anr_ingp_render takes the configuration
+        (:meth:`render_kernel_refusal`) the hash grid, the field and the composite run as
+        that one kernel, which writes nothing per sample; in reference numerics its maps
+        are ``forward``'s bit for bit, in build numerics they agree to the rounding of an
+        f32 sum taken in another order. Everything else (and ``fused=False``) runs
+        ``forward``'s own path under ``no_grad``. ``fused=True`` raises ``ANRError`` where
+        the kernel cannot serve."""
+        if fused not in ("auto", True, False):
+            raise ValueError(f"fused {fused!r}: 'auto', True or False")
+        why = self.render_kernel_refusal() if fused is not False else "fused=False"
+        if fused is True and why is not None:
+            raise _lib.ANRError(f"render(fused=True): anr_ingp_render does not take {why}")
+        with torch.no_grad():
+            if why is None and (fused is True or _RENDER_AUTO):
+                return self._render_fused(ray_batch, u, random)
+            training = self.training
+            self.training = False  # forward's occupancy update runs in training only
+            try:
+                fwd = self._forward_fused if self.fused else self._forward_reference
+                res = fwd(ray_batch, u, random=random)
+            finally:
+                self.training = training
+        return {k: res[k] for k in self._RENDER_KEYS}
+
+    def _render_fused(self, ray_batch, u, random):
+        B = ray_batch["origin"].shape[0]
+        N = self.config["num_samples_per_ray"]
+        surf_branch = self._surface_async(ray_batch)  # the per-ray surface branch, as forward
+        _, z_vals, coords = sample_and_preprocess(ray_batch, N, self._prep_ngp, random=random,
+                                                  u=u)
+        dev = coords.device
+        s = _lib.stream(dev)
+        ref = self.numerics == "reference"
+        odt = torch.float16 if ref else torch.float32
+        grid = self.pos_encoder.hash_grids[0]
+        t_hash = _lib.compute_copy(self.pos_encoder.params, self.pos_encoder.dtype)
+        mma = _lib.BF16 if self.pos_mlp.dtype == torch.bfloat16 else _lib.F16
+        pdesc, ddesc = ctypes.byref(self.pos_mlp.desc), ctypes.byref(self.dir_mlp.desc)
+        packed = torch.empty(_lib.load().anr_ingp_field_packed_size(pdesc, ddesc), device=dev,
+                             dtype=torch.float16)
+        _lib.call("anr_ingp_field_pack", pdesc, ddesc, mma,
+                  _lib.ptr(_lib.pack_source(self.pos_mlp.params, mma)),
+                  _lib.ptr(_lib.pack_source(self.dir_mlp.params, mma)), _lib.ptr(packed), s,
+                  tag="field_pack")
+        dirs = ray_batch["dir"].float().contiguous()
+        color_map, atmo, surf = (torch.empty(B, 4, device=dev, dtype=odt) for _ in range(3))
+        color_surf = surf_branch().to(odt).contiguous()
+        _lib.call("anr_ingp_render", ctypes.byref(grid.desc), _lib.ptr(coords), _lib.ptr(z_vals),
+                  _lib.ptr(dirs), B, N, _lib.ptr(t_hash), _lib.dtype_code(t_hash.dtype), pdesc,
+                  ddesc, mma, _lib.ptr(packed), _lib.ptr(color_surf), float(self.scale / 1000),
+                  _lib.RENDER_REFERENCE if ref else _lib.RENDER_BUILD, _lib.ptr(color_map),
+                  _lib.ptr(atmo), _lib.ptr(surf), s, tag="render")
+        return {"color_map_fine": color_map, "color_map_atmo": atmo, "color_map_surf": surf,
+                "z_vals_fine": z_vals}
 
     @property
     def zero_rays_total(self) -> int:

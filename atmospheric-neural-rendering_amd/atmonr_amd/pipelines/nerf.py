@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 from torch.optim import Optimizer
 
+from .._lib import ANRError
 from ..encoders import nerf_input, positional_encoding
 from ..graphics_utils import render
 from ..nerf_model import get_model
@@ -107,6 +108,32 @@ class NeRFPipeline(Pipeline):
             "fine", ray_batch, weights_coarse=results["weights_coarse"],
             z_vals_coarse=results["z_vals_coarse"], u=u_fine, noise=noise.get("fine")))
         return results
+
+    def render(self, ray_batch: Mapping[str, torch.Tensor], u=None, random: bool = False,
+               fused: bool | str = "auto") -> dict[str, torch.Tensor]:
+        """Colour maps of a batch of rays without a backward (InstantNGPPipeline.render's
+        interface): ``forward`` under ``torch.no_grad()``, returning ``color_map_fine``,
+        ``color_map_coarse`` and ``z_vals_fine``. ``u``: a pair (u_coarse, u_fine) of draws;
+        ``random=False`` (default) puts the coarse samples at the bin midpoints and the
+        fine draws at the centres of N_f equal strata, so a render is deterministic (in
+        ``eval()`` mode: a pipeline in training mode adds forward's density noise). There
+        is no fused render kernel for this pipeline: ``fused=True`` raises ``ANRError``."""
+        if fused not in ("auto", True, False):
+            raise ValueError(f"fused {fused!r}: 'auto', True or False")
+        if fused is True:
+            raise ANRError("render(fused=True): NeRFPipeline has no fused render kernel")
+        u_c, u_f = u if u is not None else (None, None)
+        B = ray_batch["origin"].shape[0]
+        dev = ray_batch["origin"].device
+        if not random:
+            s = self.config["sampler"]
+            if u_c is None:
+                u_c = torch.full((B, s["N_c"]), 0.5, device=dev)
+            if u_f is None:
+                u_f = ((torch.arange(s["N_f"], device=dev) + 0.5) / s["N_f"])[None].repeat(B, 1)
+        with torch.no_grad():
+            res = self.forward(ray_batch, u_coarse=u_c, u_fine=u_f)
+        return {k: res[k] for k in ("color_map_fine", "color_map_coarse", "z_vals_fine")}
 
     def extract(self, pts: torch.Tensor) -> torch.Tensor:
         """nerf.py:200-217: fine-model density at normalized scene points (P, 3)."""

@@ -19,6 +19,7 @@
 #pragma clang fp contract(off)
 
 #include "anr_common.h"
+#include "composite_ops.h"
 
 namespace anr {
 
@@ -29,24 +30,6 @@ static int g_composite_generic = 0;
 
 template <typename T>
 __device__ __forceinline__ float ldv(const T* p, int64_t i) { return to_f32<T>(p[i]); }
-// alpha = 1 - exp(-x) (graphics_utils.py:38) as -expm1(-x): accurate to an ulp of alpha
-// itself. Evaluated as 1 - expf(-x), f32 loses log2(1/x) bits to cancellation, and at
-// BASELINE configs[2]'s 1,024 samples per ray x = sigma * delta is ~1e-6 at
-// initialisation: dL/dcolor = w * dL/dC then carries 2e-2 relative error and the GPU
-// exp's rounding bias accumulates in the dir-MLP gradient (tools/composite_diag.py).
-__device__ __forceinline__ float alpha_of(float x) { return -expm1f(-x); }
-
-// Exclusive multiplicative scan across the wave (lane 0 gets 1).
-__device__ __forceinline__ float wave_excl_prod(float v, int lane) {
-  float incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = shfl_up(incl, d);
-    if (lane >= d) incl *= o;
-  }
-  const float ex = shfl_up(incl, 1);
-  return lane == 0 ? 1.0f : ex;
-}
 // Exclusive multiplicative suffix scan (lane 63 gets 1).
 __device__ __forceinline__ float wave_excl_suffix_prod(float v, int lane) {
   float incl = v;
@@ -57,11 +40,6 @@ __device__ __forceinline__ float wave_excl_suffix_prod(float v, int lane) {
   }
   const float ex = shfl_down(incl, 1);
   return lane == 63 ? 1.0f : ex;
-}
-__device__ __forceinline__ float wave_prod(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v *= shfl_xor(v, m);
-  return v;
 }
 // Reverse affine scan: lane holds map x -> A*x + B for its block; returns the value
 // entering the lane's block from the right, i.e. (composition of lanes > l)(0).

@@ -31,7 +31,9 @@
 #include <type_traits>
 
 #include "anr_common.h"
+#include "composite_ops.h"
 #include "hash_levels.h"
+#include "ref16_ops.h"
 
 // Profiling ablations (tools/field_ablate.sh); 0 in every product build. Bits:
 // 1 no dW MFMAs, 2 no layer-input stores, 4 no gradient-tile stores, 8 no mask reads.
@@ -1016,6 +1018,248 @@ hf_fwd_kernel(Args a, HashArgs h) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Forward-only render (anr_ingp_render): hf_fwd_kernel's hash and field phases with the
+// composite behind them, nothing written per sample. One wavefront renders one ray and
+// takes its n_per_ray / 64 segments in order:
+//  1. hash phase, one lane per sample: plane_quad into the wavefront's LDS stage only;
+//  2. field phase: the four 16-sample tiles through tile_forward (the MFMA sequence of
+//     fwd_kernel, so sigma and colour are anr_ingp_field_fwd's / _fwd_h's values bit for
+//     bit); the g == 0 lanes, which hold a sample's density and 4 colours in the C layout,
+//     put them into LDS at the sample's slot;
+//  3. composite phase, one lane per sample again, with the carries that cross a segment
+//     boundary in registers (RefCarry / BuildCarry).
+// REF = true (reference numerics): the arithmetic of ref16::fwd_kernel on the f16-rounded
+// sigma and colour. Its f16 cumprod accumulator, f32 product and f32 band sums are serial
+// chains in sample order with no other order that rounds the same way, so they run as
+// 64-step chains per segment: lane 0 walks the cumprod and the product over the segment's
+// q2 in LDS, lanes 0..3 a band sum each over the products h(colour * w). The carries (cp,
+// pr in lane 0, the band sums in lanes 0..3) are the accumulators themselves, so the
+// chain over all segments is the one fwd_kernel forms: bit-identical maps.
+// REF = false (build numerics): composite.hip's per-sample f32 expressions; the
+// transmittance is a wave scan inside the segment times the carry of the segments before
+// it, the band sums and the surface product accumulate per lane and are reduced across
+// the wave once per ray. The order of the f32 sums differs from rb::fwd_kernel's, so this
+// form is held to a tolerance against it, not to bits.
+struct RenderArgs {
+  const float* z;   // (B, n_per_ray) f32, as the sampler wrote it
+  float zs;         // z_scale
+  const void* cs;   // (B, 4) surface colour, nullable: f16 (REF) or f32
+  void* cmap;       // (B, 4) outputs: f16 (REF) or f32; atmo / surf nullable
+  void* atmo;
+  void* surf;
+  int64_t B;
+};
+
+constexpr int kRenderPad = 72;  // LDS row of a segment's f16 values (ref16.hip kPad)
+struct __attribute__((aligned(16))) RenderRefLds {
+  _Float16 q2[kRenderPad];
+  _Float16 T[kRenderPad];
+  _Float16 t[4][kRenderPad];  // f16(f16(color) * w) per band
+};
+struct RenderNoLds {};
+
+struct RefCarry {
+  _Float16 cp = 1.0f;  // lane 0: the cumprod's f16 accumulator
+  float pr = 1.0f;     // lane 0: prod over samples of q2, f32 accumulator
+  float acc = 0.0f;    // lane c < 4: band c's sum over samples, f32 accumulator
+};
+
+// One segment in reference numerics: sg / col are the f16 values of the sample in this lane
+// (sample i = s0 + lane of N), zm / z0 / zp the raw z at i - 1, i, i + 1.
+__device__ __forceinline__ void render_seg_ref(RenderRefLds& L, RefCarry& k, float sg,
+                                               const float (&col)[4], float zm, float z0,
+                                               float zp, float zs, int i, int N, int lane) {
+#pragma clang fp contract(off)
+  using namespace ::anr::ref16;
+  const Sample sm = sample(sg, delta_z(zm, z0, zp, zs, i, N));
+  L.q2[lane] = static_cast<_Float16>(sm.q2);
+  wave_sync();
+  if (lane == 0) {
+    for (int l8 = 0; l8 < 64; l8 += 8) {
+      const h8 q = *reinterpret_cast<const h8*>(&L.q2[l8]);
+      h8 tv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        tv[j] = k.cp;                  // cumprod(...)[:, :-1]
+        k.cp = k.cp * q[j];            // = h(cp * q2)
+        k.pr = mul_h(k.pr, q[j]);      // (1 - alpha).prod
+      }
+      *reinterpret_cast<h8*>(&L.T[l8]) = tv;
+    }
+  }
+  wave_sync();
+  const float w = h(sm.alpha * static_cast<float>(L.T[lane]));  // alpha * T
+#pragma unroll
+  for (int c = 0; c < 4; ++c) L.t[c][lane] = static_cast<_Float16>(h(col[c] * w));
+  wave_sync();
+  if (lane < 4) {
+    for (int l8 = 0; l8 < 64; l8 += 8) {
+      const h8 tv = *reinterpret_cast<const h8*>(&L.t[lane][l8]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) k.acc = add_h(k.acc, tv[j]);
+    }
+  }
+  wave_sync();
+}
+
+// The ray's maps from the carries (ref16::fwd_kernel's epilogue): lane c < 4 writes band c.
+__device__ __forceinline__ void render_end_ref(const RenderArgs& r, const RefCarry& k, int64_t b,
+                                               int lane) {
+#pragma clang fp contract(off)
+  using namespace ::anr::ref16;
+  const float prr = h(__shfl(k.pr, 0));
+  if (lane < 4) {
+    const __half* cs = static_cast<const __half*>(r.cs);
+    const int64_t o = b * 4 + lane;
+    const float atmo = h(k.acc);
+    const float surf = cs ? h(prr * h(__half2float(cs[o]))) : 0.0f;
+    static_cast<__half*>(r.cmap)[o] = __float2half_rn(cs ? h(atmo + surf) : atmo);
+    if (r.atmo) static_cast<__half*>(r.atmo)[o] = __float2half_rn(atmo);
+    if (r.surf && cs) static_cast<__half*>(r.surf)[o] = __float2half_rn(surf);
+  }
+}
+
+struct BuildCarry {
+  float T = 1.0f;    // uniform: the transmittance entering the segment
+  float pom = 1.0f;  // per lane: product of (1 - alpha) over the lane's samples
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // per lane: sums of colour * w
+};
+
+// One segment in build numerics (composite.hip's expressions, rb::deltas' delta).
+__device__ __forceinline__ void render_seg_build(BuildCarry& k, float sg, const float (&col)[4],
+                                                 float zm, float z0, float zp, float zs, int i,
+                                                 int N, int lane) {
+#pragma clang fp contract(off)
+  const float zi = z0 * zs, zprev = zm * zs, znext = zp * zs;
+  const float lo = i == 0 ? zi * 0.0f : (zprev + zi) / 2.0f;
+  const float hi = i == N - 1 ? zi : (zi + znext) / 2.0f;
+  const float dl = hi - lo;
+  const float al = alpha_of(sg * dl);
+  const float t = (1.0f - al) + 1e-10f;
+  const float Tin = k.T * wave_excl_prod(t, lane);
+  const float w = al * Tin;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) k.acc[c] += col[c] * w;
+  k.pom *= 1.0f - al;
+  k.T = shfl(Tin * t, 63);
+}
+
+__device__ __forceinline__ void render_end_build(const RenderArgs& r, const BuildCarry& k,
+                                                 int64_t b, int lane) {
+#pragma clang fp contract(off)
+  const float stot = wave_prod(k.pom);
+  float atmo[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) atmo[c] = wave_sum(k.acc[c]);
+  if (lane < 4) {
+    const float* cs = static_cast<const float*>(r.cs);
+    const int64_t o = b * 4 + lane;
+    const float at = lane == 0 ? atmo[0] : lane == 1 ? atmo[1] : lane == 2 ? atmo[2] : atmo[3];
+    const float surf = cs ? stot * cs[o] : 0.0f;
+    static_cast<float*>(r.cmap)[o] = at + surf;
+    if (r.atmo) static_cast<float*>(r.atmo)[o] = at;
+    if (r.surf && cs) static_cast<float*>(r.surf)[o] = surf;
+  }
+}
+
+template <int W, int NHD, bool BF, bool REF, int WAVES, int OCC, int DEDUP>
+__global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)))
+render_kernel(Args a, HashArgs h, RenderArgs r) {
+  using N = Net<W, NHD>;
+  typedef uint32_t u4q __attribute__((vector_size(16)));
+  __shared__ __attribute__((aligned(16))) _Float16 wsm[N::n_fwd];
+  // per wavefront: quad q of lane l's sample at stage[wave][q][l]
+  __shared__ __attribute__((aligned(16))) u4q stage[WAVES][4][64];
+  // per wavefront: the segment's field outputs, sigma at [0][sample], band c at [1 + c][sample]
+  __shared__ float outs[WAVES][5][64];
+  __shared__ typename std::conditional<REF, RenderRefLds, RenderNoLds>::type scan[WAVES];
+  const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int e = threadIdx.x * 8; e < N::n_fwd; e += 64 * WAVES * 8)
+    *reinterpret_cast<h8*>(wsm + e) = *reinterpret_cast<const h8*>(a.packed + e);
+  __syncthreads();  // the only block-wide barrier: the ray loop below is per wavefront
+  const __amdgpu_buffer_rsrc_t rx = wave_rsrc(h.x, h.x_bytes);
+  const __amdgpu_buffer_rsrc_t rt = wave_rsrc(h.table, h.table_bytes);
+  const int n = static_cast<int>(a.n_per_ray);
+  const int64_t rstride = static_cast<int64_t>(gridDim.x) * WAVES;
+  for (int64_t b = static_cast<int64_t>(blockIdx.x) * WAVES + wave; b < r.B; b += rstride) {
+    const const_f32* d = (const_f32*)(a.dirs + b * 3);
+    auto sdir = [&](int k) {
+      return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, d[k])));
+    };
+    Rows cur;
+    cur.dx = sdir(0) * 2.0f - 1.0f;
+    cur.dy = sdir(1) * 2.0f - 1.0f;
+    cur.dz = sdir(2) * 2.0f - 1.0f;
+    cur.dc = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    cur.ds = 0.0f;
+    const float* zr = r.z + b * n;
+    typename std::conditional<REF, RefCarry, BuildCarry>::type carry;
+#pragma unroll 1
+    for (int s0 = 0; s0 < n; s0 += 64) {
+      const int i = s0 + lane;
+      // z of the sample and of its neighbours (across a segment edge: from the row), in
+      // flight during the hash and field phases
+      const float z0 = zr[i];
+      const float zm = i > 0 ? zr[i - 1] : 0.0f;
+      const float zp = i < n - 1 ? zr[i + 1] : 0.0f;
+      // ---- hash phase: lane = sample (every sample of the ray is in range)
+      const uint32_t m = static_cast<uint32_t>(b * n + i);
+      const auto xr = __builtin_amdgcn_raw_buffer_load_b96(rx, m * 12u, 0, 0);
+      const float xv[3] = {__uint_as_float(xr[0]), __uint_as_float(xr[1]), __uint_as_float(xr[2])};
+#pragma unroll 1
+      for (int q = 0; q < 4; ++q) {
+        uint32_t p[4];
+        plane_quad<3, __half, DEDUP>(h.G, 16, q, xv, rt, p);
+        stage[wave][q][lane] = u4q{p[0], p[1], p[2], p[3]};
+      }
+      ::anr::ref16::wave_sync();
+      // ---- field phase
+#pragma unroll 1
+      for (int t = 0; t < 4; ++t) {
+        cur.xe = __builtin_bit_cast(h8, stage[wave][g][16 * t + li]);
+        const bool valid = true;
+        int zoff = 0;  // opaque fragment base, as hf_fwd_kernel
+        asm volatile("" : "+v"(zoff));
+        const LdsWeights<W, NHD> fw{wsm + zoff, lane};
+        Tile<W, NHD> tt;
+        tile_forward<W, NHD, 1, BF, 1>(fw, &cur, &valid, g, &tt, NoSink{});
+        if (g == 0) {
+          const float sv = fmaxf(tt.po[0], 0.0f);
+          const f4 cv = {fmaxf(tt.col[0], 0.0f), fmaxf(tt.col[1], 0.0f), fmaxf(tt.col[2], 0.0f),
+                         fmaxf(tt.col[3], 0.0f)};
+          if constexpr (REF) {  // anr_ingp_field_fwd_h's roundings
+            const h4 ch = to_h4<false>(cv);
+            outs[wave][0][16 * t + li] = static_cast<float>(static_cast<_Float16>(sv));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) outs[wave][1 + c][16 * t + li] = static_cast<float>(ch[c]);
+          } else {
+            outs[wave][0][16 * t + li] = sv;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) outs[wave][1 + c][16 * t + li] = cv[c];
+          }
+        }
+      }
+      ::anr::ref16::wave_sync();
+      // ---- composite phase: lane = sample
+      const float sg = outs[wave][0][lane];
+      const float col[4] = {outs[wave][1][lane], outs[wave][2][lane], outs[wave][3][lane],
+                            outs[wave][4][lane]};
+      if constexpr (REF)
+        render_seg_ref(scan[wave], carry, sg, col, zm, z0, zp, r.zs, i, n, lane);
+      else
+        render_seg_build(carry, sg, col, zm, z0, zp, r.zs, i, n, lane);
+      // the next segment's stage / outs writes stay behind this segment's reads
+      ::anr::ref16::wave_sync();
+    }
+    if constexpr (REF)
+      render_end_ref(r, carry, b, lane);
+    else
+      render_end_build(r, carry, b, lane);
   }
 }
 
@@ -2342,6 +2586,56 @@ static int dispatch_hf_t(int v, const Args& a, const HashArgs& h, hipStream_t st
   return 1;
 }
 
+// forward-only render: a persistent grid of RN_WAVES-wavefront blocks, a wavefront per ray.
+// The grid is what the current device holds at once: its CU count times the occupancy
+// query's blocks per CU, both asked per device and kept (no allocation, no synchronisation).
+constexpr int RN_WAVES = 8;
+constexpr int RN_OCC = 4;
+static int64_t render_grid(const void* fn, int threads, int64_t work_blocks) {
+  static std::mutex mu;
+  static std::unordered_map<uint64_t, int64_t> cache;  // (device, kernel) -> resident blocks
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  int64_t cap;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    int64_t& c = cache[(static_cast<uint64_t>(dev) << 56) ^ reinterpret_cast<uintptr_t>(fn)];
+    if (c == 0) {
+      int cus = 0, per_cu = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          cus < 1)
+        cus = 1;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess ||
+          per_cu < 1)
+        per_cu = 1;
+      c = static_cast<int64_t>(cus) * per_cu;
+    }
+    cap = c;
+  }
+  const int64_t blocks = work_blocks < cap ? work_blocks : cap;
+  return blocks < 1 ? 1 : blocks;
+}
+template <int W, int NHD, bool BF, bool REF>
+static int run_render(const Args& a, const HashArgs& h, const RenderArgs& r, hipStream_t st) {
+  const void* fn =
+      reinterpret_cast<const void*>(&render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>);
+  const int64_t blocks = render_grid(fn, 64 * RN_WAVES, (r.B + RN_WAVES - 1) / RN_WAVES);
+  hipLaunchKernelGGL((render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>), dim3(blocks),
+                     dim3(64 * RN_WAVES), 0, st, a, h, r);
+  return 0;
+}
+template <bool BF, bool REF>
+static int dispatch_render(int v, const Args& a, const HashArgs& h, const RenderArgs& r,
+                           hipStream_t st) {
+  switch (v) {
+    case 321: return run_render<32, 1, BF, REF>(a, h, r, st);
+    case 322: return run_render<32, 2, BF, REF>(a, h, r, st);
+    case 641: return run_render<64, 1, BF, REF>(a, h, r, st);
+    case 642: return run_render<64, 2, BF, REF>(a, h, r, st);
+  }
+  return 1;
+}
+
 template <bool BF>
 static int dispatch_t(int v, int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
   switch (v) {
@@ -2594,6 +2888,74 @@ extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const floa
                                        : dispatch_hf_t<false>(v, a, h, st);
   ANR_CHECK_ARG(rc == 0, "anr_ingp_hash_field_fwd: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_hash_field_fwd");
+  return ANR_OK;
+}
+
+extern "C" int anr_ingp_render(const anr_hashgrid_desc* grid, const float* coords, const float* z,
+                               const float* dirs, int64_t B, int64_t n_per_ray, const void* table,
+                               int32_t table_dtype, const anr_mlp_desc* pos,
+                               const anr_mlp_desc* dir, int32_t mma_dtype, const void* packed,
+                               const void* color_surf, float z_scale, int32_t numerics,
+                               void* color_map, void* atmo, void* surf, anr_stream_t stream) {
+  ANR_CHECK_ARG(B >= 0, "anr_ingp_render: bad B");
+  if (B == 0) return ANR_OK;
+  ANR_CHECK_ARG(grid && coords && z && dirs && table && pos && dir && packed && color_map,
+                "anr_ingp_render: null pointer (color_surf, atmo and surf may be null)");
+  ANR_CHECK_ARG(numerics == ANR_RENDER_BUILD || numerics == ANR_RENDER_REFERENCE,
+                "anr_ingp_render: numerics must be ANR_RENDER_BUILD or ANR_RENDER_REFERENCE");
+  const int v = variant(pos, dir);
+  if (v != 0 && n_sigma(dir) > 1) return refuse_bands("anr_ingp_render");
+  if (v == 0 || !mma_ok(mma_dtype) || table_dtype != ANR_F16 || grid->n_dims != 3 ||
+      grid->n_features != 2 || grid->n_levels != 16 || dir->n_output != 4 || n_per_ray < 64 ||
+      n_per_ray % 64 != 0) {
+    ::anr::set_error("anr_ingp_render: unsupported configuration (3-D f16 grid of 16 levels x 2 "
+                     "features, a supported field pair with one density and 4 colour outputs, "
+                     "f16 or bf16 MFMA, samples per ray a positive multiple of 64)");
+    return ANR_E_UNSUPPORTED;
+  }
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) {
+    ::anr::set_error("anr_ingp_render: unsupported: packed weights must be 16-byte aligned");
+    return ANR_E_UNSUPPORTED;
+  }
+  ::anr::GridLevels G;
+  ANR_CHECK_ARG(::anr::make_levels(grid, &G), "anr_ingp_render: descriptor not initialised");
+  const int64_t lim = int64_t(1) << 31;
+  const int64_t t_bytes = static_cast<int64_t>(G.offset[15] + G.size[15]) * 4;
+  if (n_per_ray >= lim || B >= lim / n_per_ray || (B * n_per_ray + 64) * 12 >= lim ||
+      t_bytes >= lim) {
+    ::anr::set_error("anr_ingp_render: unsupported: byte ranges must stay below 2^31");
+    return ANR_E_UNSUPPORTED;
+  }
+  const int64_t M = B * n_per_ray;
+  Args a{};
+  a.packed = static_cast<const _Float16*>(packed);
+  a.dirs = dirs;
+  a.n_per_ray = static_cast<uint32_t>(n_per_ray);
+  a.M = M;
+  a.n_out = 4;
+  HashArgs h{};
+  h.G = G;
+  h.x = coords;
+  h.x_bytes = static_cast<uint32_t>(M * 12);
+  h.table = static_cast<const __half*>(table);
+  h.table_bytes = static_cast<uint32_t>(t_bytes);
+  RenderArgs r{};
+  r.z = z;
+  r.zs = z_scale;
+  r.cs = color_surf;
+  r.cmap = color_map;
+  r.atmo = atmo;
+  r.surf = surf;
+  r.B = B;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const bool bf = mma_dtype == ANR_BF16;
+  const int rc = numerics == ANR_RENDER_REFERENCE
+                     ? (bf ? dispatch_render<true, true>(v, a, h, r, st)
+                           : dispatch_render<false, true>(v, a, h, r, st))
+                     : (bf ? dispatch_render<true, false>(v, a, h, r, st)
+                           : dispatch_render<false, false>(v, a, h, r, st));
+  ANR_CHECK_ARG(rc == 0, "anr_ingp_render: no kernel for this shape");
+  ANR_CHECK_LAUNCH("anr_ingp_render");
   return ANR_OK;
 }
 

@@ -30,6 +30,8 @@ extern "C" {
 #endif
 
 /* Added to ABI 5 without a version change (additive; every ABI 5 call behaves as it did):
+ * anr_ingp_render -- the forward-only render (hash grid, field and composite in one kernel,
+ * no per-sample output), in reference and build numerics;
  * multi-band extinction in the fused field -- dir descriptors of 16..18 inputs (S = 20 -
  * n_input = 2..4 density outputs), refused before, are accepted by anr_ingp_field_supported
  * / _packed_size / _pack / _fwd / _density / _bwd / _bwd_workspace_bytes, with sigma and
@@ -425,6 +427,36 @@ int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const float* x, int64
                             const anr_mlp_desc* dir, int32_t mma_dtype, const void* packed,
                             const float* dirs, int64_t n_per_ray, float* sigma, float* color,
                             int64_t color_stride, anr_stream_t stream);
+/* Forward-only render: hash grid, field and composite in one kernel, nothing written per
+ * sample. Replaces, for a render without a backward, instant_ngp.py:163-192 (the tcnn
+ * Encoding forward, pos_mlp, dir_encoder, dir_mlp and the render_with_surface call) and
+ * graphics_utils.py:6-77 (render / render_with_surface). One wavefront per ray walks the
+ * ray's 64-sample segments in order; sigma and colour are anr_ingp_field_fwd's values
+ * (anr_ingp_field_fwd_h's in reference numerics) and never leave the chip.
+ *   coords (B * n_per_ray, 3) f32 and z (B, n_per_ray) f32 as anr_sample_uniform_bins writes
+ *   them, dirs (B, 3) f32, table: the grid's f16 table, packed: anr_ingp_field_pack's buffer.
+ *   numerics ANR_RENDER_REFERENCE: the arithmetic of anr_composite_ref16_fwd on the f16
+ *   sigma / colour; color_surf (B, 4) and the outputs are f16; the maps are bit-identical to
+ *   anr_ingp_field_fwd_h followed by anr_composite_ref16_fwd.
+ *   numerics ANR_RENDER_BUILD: anr_composite_fwd's f32 expressions on the f32 sigma / colour;
+ *   color_surf and the outputs are f32; the f32 sums run in another order than
+ *   anr_composite_fwd's, so the maps agree with it to rounding, not to bits.
+ *   color_map, atmo, surf: (B, 4) contiguous; color_surf, atmo and surf may be null (surf is
+ *   written only with a color_surf; without one color_map is the atmospheric map).
+ * Shapes: 3-D f16 hash grid of 16 levels x 2 features, a supported field pair with one
+ * density and 4 colour outputs (W in {32, 64}, one or two hidden dir layers), mma_dtype
+ * ANR_F16 or ANR_BF16, n_per_ray a positive multiple of 64, 16-byte aligned packed weights,
+ * byte ranges below 2^31; ANR_E_UNSUPPORTED otherwise. B = 0: ANR_OK without a launch.
+ * Allocates nothing and does not synchronise; the grid is sized from the current device's
+ * CU count and the occupancy query. */
+#define ANR_RENDER_BUILD 0
+#define ANR_RENDER_REFERENCE 1
+int anr_ingp_render(const anr_hashgrid_desc* grid, const float* coords, const float* z,
+                    const float* dirs, int64_t B, int64_t n_per_ray, const void* table,
+                    int32_t table_dtype, const anr_mlp_desc* pos, const anr_mlp_desc* dir,
+                    int32_t mma_dtype, const void* packed, const void* color_surf,
+                    float z_scale, int32_t numerics, void* color_map, void* atmo, void* surf,
+                    anr_stream_t stream);
 /* Density only: sigma[r] = relu(pos_mlp(enc[r])[0]) (f32; (M, S) for S > 1), bit-identical to
  * anr_ingp_field_fwd's sigma, without the dir MLP -- the extract loop
  * (scripts/extract.py:203-209 -> instant_ngp.py:208-247 reads only the extinction) and the

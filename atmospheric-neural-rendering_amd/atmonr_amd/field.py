@@ -95,13 +95,7 @@ class IngpFieldFn(torch.autograd.Function):
             raise _lib.ANRError("multi-band extinction runs the fused field in build numerics "
                                 "without occupancy culling")
         if fused:
-            mma = _mma_code(pipe)
-            pdesc, ddesc = ctypes.byref(pos_mod.desc), ctypes.byref(pipe.dir_mlp.desc)
-            packed = torch.empty(_lib.load().anr_ingp_field_packed_size(pdesc, ddesc),
-                                 device=dev, dtype=torch.float16)  # 16-bit carrier
-            m_pos, m_dir = _lib.pack_source(p_pos, mma), _lib.pack_source(p_dir, mma)
-            call("anr_ingp_field_pack", pdesc, ddesc, mma, ptr(m_pos), ptr(m_dir), ptr(packed),
-                 s, tag="field_pack")
+            pdesc, ddesc, mma, packed = pack_weights(pipe, dev, s, (p_pos, p_dir))
             nb = pipe.dir_mlp.n_output_dims
         if planes and rows is None and n_sig == 1 and _hash_field_ok(grid, nb, n_per_ray):
             # hash grid + field forward in one kernel (anr_ingp_hash_field_fwd): the level-
@@ -329,6 +323,21 @@ def _mma_code(pipe) -> int:
     return _lib.BF16 if pipe.pos_mlp.dtype == torch.bfloat16 else _lib.F16
 
 
+def pack_weights(pipe, dev, stream, params=None):
+    """The fused field's weights in MFMA fragment order (anr_ingp_field_pack), packed from
+    ``params`` = (pos, dir) parameter tensors, the pipeline's own by default. Returns
+    (pdesc, ddesc, mma, packed): the two descriptors by reference, the MFMA dtype code and
+    the packed buffer, as every field entry point takes them."""
+    p_pos, p_dir = params if params is not None else (pipe.pos_mlp.params, pipe.dir_mlp.params)
+    mma = _mma_code(pipe)
+    pdesc, ddesc = ctypes.byref(pipe.pos_mlp.desc), ctypes.byref(pipe.dir_mlp.desc)
+    packed = torch.empty(_lib.load().anr_ingp_field_packed_size(pdesc, ddesc), device=dev,
+                         dtype=torch.float16)  # 16-bit carrier
+    call("anr_ingp_field_pack", pdesc, ddesc, mma, ptr(_lib.pack_source(p_pos, mma)),
+         ptr(_lib.pack_source(p_dir, mma)), ptr(packed), stream, tag="field_pack")
+    return pdesc, ddesc, mma, packed
+
+
 def _enc_planes(grid, M: int) -> bool:
     """The fused field reads the hash features as level-quad planes (default) or, with
     ANR_ENC_PLANES=0 (A/B), in the row layout of the walker forward. The planes kernel
@@ -408,12 +417,7 @@ def field_density(pipe, pts: torch.Tensor, run_length: int = 0) -> torch.Tensor:
          int(run_length),
          ptr(t_hash), dtype_code(t_hash.dtype), ptr(enc), _lib.F16, enc.stride(0), s,
          tag="hash_fwd")
-    mma = _mma_code(pipe)
-    pdesc, ddesc = ctypes.byref(pos_mod.desc), ctypes.byref(pipe.dir_mlp.desc)
-    packed = torch.empty(_lib.load().anr_ingp_field_packed_size(pdesc, ddesc), device=dev,
-                         dtype=torch.float16)
-    call("anr_ingp_field_pack", pdesc, ddesc, mma, ptr(_lib.pack_source(pos_mod.params, mma)),
-         ptr(_lib.pack_source(pipe.dir_mlp.params, mma)), ptr(packed), s, tag="field_pack")
+    pdesc, ddesc, mma, packed = pack_weights(pipe, dev, s)
     # the pos MLP only (anr_ingp_field_density): sigma bit-identical to the full field's
     call("anr_ingp_field_density", pdesc, ddesc, mma, ptr(packed), ptr(enc), enc.stride(0), P,
          ptr(sigma), s, tag="field_density")

@@ -61,7 +61,7 @@ import torch.nn.functional as F
 from torch.optim import Optimizer
 
 from .. import _lib
-from ..field import IngpFieldFn, field_density, field_fused
+from ..field import IngpFieldFn, field_density, field_fused, pack_weights
 from ..graphics_utils import render_with_surface, render_with_surface_ref16
 from ..losses import LOSSES, indexed_loss, indexed_loss_ref16
 from ..occupancy import OccupancyGrid, pipeline_density
@@ -455,14 +455,7 @@ class InstantNGPPipeline(Pipeline):
         odt = torch.float16 if ref else torch.float32
         grid = self.pos_encoder.hash_grids[0]
         t_hash = _lib.compute_copy(self.pos_encoder.params, self.pos_encoder.dtype)
-        mma = _lib.BF16 if self.pos_mlp.dtype == torch.bfloat16 else _lib.F16
-        pdesc, ddesc = ctypes.byref(self.pos_mlp.desc), ctypes.byref(self.dir_mlp.desc)
-        packed = torch.empty(_lib.load().anr_ingp_field_packed_size(pdesc, ddesc), device=dev,
-                             dtype=torch.float16)
-        _lib.call("anr_ingp_field_pack", pdesc, ddesc, mma,
-                  _lib.ptr(_lib.pack_source(self.pos_mlp.params, mma)),
-                  _lib.ptr(_lib.pack_source(self.dir_mlp.params, mma)), _lib.ptr(packed), s,
-                  tag="field_pack")
+        pdesc, ddesc, mma, packed = pack_weights(self, dev, s)
         dirs = ray_batch["dir"].float().contiguous()
         color_map, atmo, surf = (torch.empty(B, 4, device=dev, dtype=odt) for _ in range(3))
         color_surf = surf_branch().to(odt).contiguous()

@@ -41,27 +41,65 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 constexpr int kWave = 64;  // CDNA wavefront width
 
 // ---------------------------------------------------------------- launch geometry
-// Blocks of kernel `fn` that one CU holds at once, at `threads` per block and `lds` bytes
-// of dynamic LDS. Queried once per kernel; a failed query counts as 1.
-inline int blocks_per_cu(const void* fn, int threads, size_t lds = 0) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, int> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  int& per_cu = cache[fn];
-  if (per_cu == 0) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, lds) != hipSuccess || nb < 1)
-      nb = 1;
-    per_cu = nb;
+// One mutex and one map serve both queries below. Each answer is asked for once per key and
+// kept (no allocation, no synchronisation afterwards); a failed query counts as 1.
+struct GeomCache {
+  std::mutex mu;
+  std::unordered_map<uint64_t, int64_t> cus;     // device -> CU count
+  std::unordered_map<uint64_t, int64_t> blocks;  // (device, kernel) -> resident blocks
+  static GeomCache& get() {
+    static GeomCache c;
+    return c;
   }
-  return per_cu;
+  int64_t cus_locked(int dev) {
+    int64_t& n = cus[static_cast<uint64_t>(dev)];
+    if (n == 0) {
+      int v = 0;
+      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
+        v = 1;
+      n = v;
+    }
+    return n;
+  }
+};
+
+inline int current_device() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess ? dev : 0;
 }
 
-// Grid of a persistent kernel: a block per `work_blocks` up to what the chip's 256 CUs hold
-// at once, and at least one.
-inline int64_t persistent_blocks(int64_t work_blocks, int per_cu) {
-  const int64_t cap = 256LL * per_cu;
-  const int64_t blocks = work_blocks < cap ? work_blocks : cap;
+// Compute units of the current device.
+inline int64_t device_cus() {
+  GeomCache& c = GeomCache::get();
+  const int dev = current_device();
+  std::lock_guard<std::mutex> lock(c.mu);
+  return c.cus_locked(dev);
+}
+
+// Blocks of kernel `fn` that the current device holds at once, at `threads` per block and
+// `lds` bytes of dynamic LDS: its CU count times the occupancy query's blocks per CU.
+// Kept per (device, kernel) alone: every kernel here has one launch shape, so `threads` and
+// `lds` are not part of the key.
+inline int64_t resident_blocks(const void* fn, int threads, size_t lds = 0) {
+  GeomCache& c = GeomCache::get();
+  const int dev = current_device();
+  std::lock_guard<std::mutex> lock(c.mu);
+  int64_t& blocks =
+      c.blocks[(static_cast<uint64_t>(dev) << 56) ^ reinterpret_cast<uintptr_t>(fn)];
+  if (blocks == 0) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess ||
+        per_cu < 1)
+      per_cu = 1;
+    blocks = c.cus_locked(dev) * per_cu;
+  }
+  return blocks;
+}
+
+// Grid of a persistent kernel: a block per `work_blocks` up to the `resident` blocks the
+// device holds at once, and at least one.
+inline int64_t persistent_blocks(int64_t work_blocks, int64_t resident) {
+  const int64_t blocks = work_blocks < resident ? work_blocks : resident;
   return blocks < 1 ? 1 : blocks;
 }
 

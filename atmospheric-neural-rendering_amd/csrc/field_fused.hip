@@ -2297,44 +2297,125 @@ static int g_target_log2 = 6;  // f16 gradient scale: max |dL/dout| of a wavefro
 // the general kernel; test / A-B hook anr_ingp_field_force_fwd
 static int g_fwd_ut = 1;
 
+// ---- run-time values as compile-time tags: each helper calls `f` with the tag of its value
+// and answers `none` for a value it has no kernels for
+template <int W_, int NHD_>
+struct NetTag {
+  static constexpr int W = W_, NHD = NHD_;
+};
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// v: variant() of a pos/dir pair, 10 W + NHD
+template <typename R, typename F>
+static R with_net(int v, R none, F&& f) {
+  switch (v) {
+    case 321: return f(NetTag<32, 1>{});
+    case 322: return f(NetTag<32, 2>{});
+    case 641: return f(NetTag<64, 1>{});
+    case 642: return f(NetTag<64, 2>{});
+  }
+  return none;
+}
+// ns: the pair's density outputs (n_sigma)
+template <typename R, typename F>
+static R with_bands(int ns, R none, F&& f) {
+  switch (ns) {
+    case 1: return f(int_c<1>{});
+    case 2: return f(int_c<2>{});
+    case 3: return f(int_c<3>{});
+    case 4: return f(int_c<4>{});
+  }
+  return none;
+}
+template <typename F>
+static auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(net, bands, bf) for a (variant, n_sigma, bf16 MFMA) triple
+template <typename R, typename F>
+static R with_variant(int v, int ns, bool bf, R none, F&& f) {
+  return with_net(v, none, [&](auto net) {
+    return with_bands(ns, none, [&](auto s) {
+      return with_bool(bf, [&](auto b) { return f(net, s, b); });
+    });
+  });
+}
+
+// ---- launch plans: one per pass, for every S. They launch only kernels the library has
+// always had: a form without one (S > 1 with rows, f16 outputs, f16 gradients or reference
+// numerics; bf16 with reference numerics) answers no_kernel, behind `if constexpr` so that no
+// kernel is instantiated for it.
+enum class Plan { ok, no_kernel, workspace };
+
+constexpr int kBlockWaves = 4;  // wavefronts per block of the forward, density and backward kernels
+using FieldKernel = void (*)(Args);
+using BwdKernel = void (*)(Args, float, int64_t, const float*);
+
+// a grid-stride pass over 16-row tiles, a tile per wavefront, on at most `resident` blocks
+static Plan launch_tiles16(FieldKernel k, int64_t resident, const Args& a, hipStream_t st) {
+  const int64_t tiles = (a.M + 15) / 16;
+  const int64_t blocks = persistent_blocks((tiles + kBlockWaves - 1) / kBlockWaves, resident);
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * kBlockWaves), 0, st, a);
+  return Plan::ok;
+}
+
+// the uniform-tile form (see fwd_kernel): dense rows whose 16-row tiles are one ray each,
+// 4 colour outputs in 16-byte aligned rows, byte offsets of the outputs (`out_bytes` per
+// element) below 2^31. S <= 4 <= color_stride: the sigma offsets stay below the colour rows'.
+static bool fwd_uniform(const Args& a, int out_bytes) {
+  return g_fwd_ut && a.rows == nullptr && a.n_per_ray % 16 == 0 && a.n_out == 4 &&
+         (a.color_stride & 3) == 0 && a.M * a.color_stride * out_bytes < (int64_t{1} << 31);
+}
+
+template <int W, int NHD, bool BF, int S>
+static Plan plan_fwd(const Args& a, hipStream_t st) {
+  const bool ho = a.color_h != nullptr;  // f16 outputs (same grid as the f32 form)
+  if ((ho && a.rows) || (S > 1 && (ho || a.rows))) return Plan::no_kernel;
+  const bool ut = fwd_uniform(a, ho ? 2 : 4);
+  const FieldKernel general = fwd_kernel<W, NHD, false, BF, false, false, S>;
+  FieldKernel k = ut ? fwd_kernel<W, NHD, false, BF, true, false, S> : general;
+  if constexpr (S == 1) {
+    if (ho)
+      k = ut ? fwd_kernel<W, NHD, false, BF, true, true> : fwd_kernel<W, NHD, false, BF, false, true>;
+    else if (a.rows)
+      k = fwd_kernel<W, NHD, true, BF, false>;
+  }
+  // every forward form runs the grid of the general f32 one
+  return launch_tiles16(
+      k, resident_blocks(reinterpret_cast<const void*>(general), 64 * kBlockWaves), a, st);
+}
+
+template <int W, int NHD, bool BF, int S>
+static Plan plan_density(const Args& a, hipStream_t st) {
+  // 8 blocks (32 waves) per CU, grid-stride
+  return launch_tiles16(density_kernel<W, NHD, BF, S>, 8 * device_cus(), a, st);
+}
+
 // Backward launch geometry: one resident wavefront per slot (4 per block), each owning a
 // contiguous range of 32-sample tiles. The f16 backward needs one float per wavefront of
 // caller-owned workspace for the gradient maxima; bf16 needs none.
 struct BwdGeom {
   int64_t blocks, nw, tpw;
 };
-// the grid of a 4-wave kernel with `per_cu` resident blocks per CU over M rows
-static BwdGeom tile_geom(int64_t M, int per_cu) {
-  const int waves = 4;
+// the grid of the 4-wave backward kernel `fn` over M rows
+static BwdGeom tile_geom(int64_t M, BwdKernel fn) {
   const int64_t tiles = (M + 31) / 32;
-  const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, per_cu);
-  const int64_t nw = blocks * waves;
+  const int64_t blocks = persistent_blocks(
+      (tiles + kBlockWaves - 1) / kBlockWaves,
+      resident_blocks(reinterpret_cast<const void*>(fn), 64 * kBlockWaves));
+  const int64_t nw = blocks * kBlockWaves;
   return {blocks, nw, (tiles + nw - 1) / nw};
 }
 // every backward form of one d_color layout (fast or general) runs the grid of its plain
 // (REF 0, f32-gradient) instantiation
-template <int W, int NHD, bool BF, int S = 1>
+template <int W, int NHD, bool BF, int S>
 static BwdGeom bwd_geom(int64_t M, bool fast) {
-  const void* fn =
-      fast ? reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>)
-           : reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>);
-  return tile_geom(M, blocks_per_cu(fn, 256));
+  return tile_geom(M, fast ? bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>
+                           : bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>);
 }
 
-// the reference-numerics pos pass (REF 4): its own occupancy (no dir network's registers
-// or LDS sums); the list pass (REF 3): one block per CU slot of its occupancy
-template <int W, int NHD, bool HG>
-static BwdGeom pos_geom(int64_t M) {
-  const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 4, HG>);
-  return tile_geom(M, blocks_per_cu(fn, 256));
-}
-template <int W, int NHD, bool HG>
-static int64_t list_blocks() {
-  const void* fn = reinterpret_cast<const void*>(&bwd_rt_kernel<W, NHD, true, false, false, 3, HG>);
-  return 256LL * blocks_per_cu(fn, 256);
-}
-
-template <int W, int NHD, bool BF, int S = 1>
+template <int W, int NHD, bool BF, int S>
 static int64_t bwd_workspace(int64_t M) {
   if (BF || M <= 0) return 0;
   // the larger wave count of the fast and general d_color layouts, so a workspace sized
@@ -2347,201 +2428,84 @@ static int64_t bwd_workspace(int64_t M) {
   return static_cast<int64_t>(sizeof(float)) * n;
 }
 
-template <int W, int NHD, bool BF>
-static int run(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
-  using N = Net<W, NHD>;
-  const int waves = 4;
-  if (op == 1) {
-    const int64_t tiles = (a.M + 15) / 16;
-    // every forward form runs the grid of the general f32 one
-    const void* fn = reinterpret_cast<const void*>(&fwd_kernel<W, NHD, false, BF, false>);
-    const int64_t blocks =
-        persistent_blocks((tiles + waves - 1) / waves, blocks_per_cu(fn, 64 * waves));
-    // the uniform-tile form (see fwd_kernel): dense rows whose 16-row tiles are one ray each,
-    // 4 colour outputs in 16-byte aligned rows, byte offsets of the outputs below 2^31
-    const bool ho = a.color_h != nullptr;  // f16 outputs (same grid as the f32 form)
-    const bool ut = g_fwd_ut && a.rows == nullptr && a.n_per_ray % 16 == 0 && a.n_out == 4 &&
-                    (a.color_stride & 3) == 0 &&
-                    a.M * a.color_stride * (ho ? 2 : 4) < (int64_t{1} << 31);
-#define ANR_FWD_LAUNCH(ROWSV, BSV, HOV)                                                      \
-  hipLaunchKernelGGL((fwd_kernel<W, NHD, ROWSV, BF, BSV, HOV>), dim3(blocks), dim3(64 * waves), \
-                     0, st, a)
-    if (ho) {
-      if (a.rows) return 1;
-      if (ut) ANR_FWD_LAUNCH(false, true, true);
-      else ANR_FWD_LAUNCH(false, false, true);
-    } else if (a.rows)
-      ANR_FWD_LAUNCH(true, false, false);
-    else if (ut)
-      ANR_FWD_LAUNCH(false, true, false);
-    else
-      ANR_FWD_LAUNCH(false, false, false);
-#undef ANR_FWD_LAUNCH
-    return 0;
+static void launch_bwd(BwdKernel k, int64_t blocks, const Args& a, float target, int64_t tpw,
+                       const float* wmax, hipStream_t st) {
+  hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(blocks)), dim3(64 * kBlockWaves), 0, st, a, target,
+                     tpw, wmax);
+}
+
+// reference numerics (the register-transposed kernel, REF), f16 (HG) or f32 incoming gradients
+template <int W, int NHD, bool HG>
+static Plan plan_bwd_ref(const Args& a, bool fast, hipStream_t st) {
+  if (a.d_enc_h && fast && a.tile_list) {
+    // the pos pass (REF 4) over every tile, on a grid of its own occupancy (more waves per
+    // SIMD: no dir network's registers or LDS sums in it), then the list pass (REF 3) over
+    // the tiles it left (nonzero dL/dcolor), at most one per wavefront of a grid of its
+    // occupancy
+    const BwdKernel pos = bwd_rt_kernel<W, NHD, true, false, false, 4, HG>;
+    const BwdKernel list = bwd_rt_kernel<W, NHD, true, false, false, 3, HG>;
+    const BwdGeom pg = tile_geom(a.M, pos);
+    if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess)
+      return Plan::no_kernel;
+    launch_bwd(pos, pg.blocks, a, 0.0f, pg.tpw, nullptr, st);
+    launch_bwd(list, resident_blocks(reinterpret_cast<const void*>(list), 64 * kBlockWaves), a, 0.0f,
+               0, nullptr, st);
+    return Plan::ok;
   }
-  if (op == 3) {
-    const int64_t tiles = (a.M + 15) / 16;
-    // 8 blocks (32 waves) per CU, grid-stride
-    const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, 8);
-    hipLaunchKernelGGL((density_kernel<W, NHD, BF>), dim3(blocks), dim3(64 * waves), 0, st, a);
-    return 0;
-  }
+  BwdKernel k = nullptr;
+  if (a.d_enc_h)  // f16 rows and row bits
+    k = fast ? bwd_rt_kernel<W, NHD, true, false, false, 2, HG>
+             : bwd_rt_kernel<W, NHD, false, false, false, 2, HG>;
+  else if constexpr (!HG)  // f32 rows
+    k = fast ? bwd_rt_kernel<W, NHD, true, false, false, 1>
+             : bwd_rt_kernel<W, NHD, false, false, false, 1>;
+  if (!k) return Plan::no_kernel;  // f16 gradients come with f16 rows only
+  const BwdGeom gm = bwd_geom<W, NHD, false, 1>(a.M, fast);
+  launch_bwd(k, gm.blocks, a, 0.0f, gm.tpw, nullptr, st);
+  return Plan::ok;
+}
+
+template <int W, int NHD, bool BF, int S>
+static Plan plan_bwd(const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
+  using N = Net<W, NHD, S>;
   const bool hg = a.d_color_h != nullptr;  // f16 gradients (the f16-rows forms only)
+  const bool ref = a.loss_scale > 0.0f;
   const bool fast = a.n_out == 4 && (a.d_color_stride & 3) == 0 &&
                     (hg ? a.d_sigma_h != nullptr : a.d_sigma != nullptr);
-  if (a.loss_scale > 0.0f) {  // reference numerics: the register-transposed kernel, REF
-    if constexpr (BF) {
-      return 1;
+  if (S > 1 && (a.rows || hg || ref)) return Plan::no_kernel;
+  if (ref) {
+    if constexpr (BF || S > 1) {
+      return Plan::no_kernel;
     } else {
-      if (a.rows) return 1;
-      const BwdGeom gm = bwd_geom<W, NHD, BF>(a.M, fast);
-      const dim3 grid(static_cast<unsigned>(gm.blocks)), block(64 * waves);
-#define ANR_REF_BWD(FASTV, REFV)                                                             \
-  hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, FASTV, false, false, REFV>), grid, block, 0, st, a, \
-                     0.0f, gm.tpw, nullptr)
-      if (hg) {  // the same three forms (and grids) as the f32-gradient branches below
-        if (!a.d_enc_h) return 1;
-        if (fast && a.tile_list) {
-          const BwdGeom pg = pos_geom<W, NHD, true>(a.M);
-          if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess) return 1;
-          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 4, true>),
-                             dim3(static_cast<unsigned>(pg.blocks)), block, 0, st, a, 0.0f,
-                             pg.tpw, nullptr);
-          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 3, true>),
-                             dim3(static_cast<unsigned>(list_blocks<W, NHD, true>())), block, 0,
-                             st, a, 0.0f, int64_t{0}, nullptr);
-        } else if (fast) {
-          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 2, true>), grid, block, 0,
-                             st, a, 0.0f, gm.tpw, nullptr);
-        } else {
-          hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, false, false, false, 2, true>), grid, block,
-                             0, st, a, 0.0f, gm.tpw, nullptr);
-        }
-      } else if (a.d_enc_h && fast && a.tile_list) {
-        // the pos pass over every tile (more waves per SIMD: no dir network in it), then the
-        // list pass over the tiles it left (nonzero dL/dcolor), at most one per wavefront
-        // of a grid of its occupancy
-        const BwdGeom pg = pos_geom<W, NHD, false>(a.M);
-        if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess) return 1;
-        hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 4>),
-                           dim3(static_cast<unsigned>(pg.blocks)), block, 0, st, a, 0.0f, pg.tpw,
-                           nullptr);
-        hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, false, 3>),
-                           dim3(static_cast<unsigned>(list_blocks<W, NHD, false>())), block, 0, st,
-                           a, 0.0f, int64_t{0}, nullptr);
-      } else if (a.d_enc_h) {
-        if (fast) ANR_REF_BWD(true, 2);
-        else ANR_REF_BWD(false, 2);
-      } else {
-        if (fast) ANR_REF_BWD(true, 1);
-        else ANR_REF_BWD(false, 1);
-      }
-#undef ANR_REF_BWD
-      return 0;
+      if (a.rows) return Plan::no_kernel;
+      return hg ? plan_bwd_ref<W, NHD, true>(a, fast, st) : plan_bwd_ref<W, NHD, false>(a, fast, st);
     }
   }
+  // build numerics: the wavefronts' gradient maxima (f16 only), then the fast or general kernel
   const size_t lds = static_cast<size_t>(N::n_packed) * 2 + sizeof(float) * (N::NPOS + N::NDIR);
-  if (lds > 160 * 1024) return 1;
-  const BwdGeom gm = bwd_geom<W, NHD, BF>(a.M, fast);
-  if (!BF && (ws == nullptr || ws_bytes < static_cast<int64_t>(sizeof(float)) * gm.nw))
-    return 2;
-  const float target = ldexpf(1.0f, g_target_log2);
-  const dim3 grid(static_cast<unsigned>(gm.blocks)), block(64 * waves);
-  if (!BF) {
-    if (a.rows)
-      hipLaunchKernelGGL(absmax_kernel<true>, dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32, ws);
-    else
-      hipLaunchKernelGGL(absmax_kernel<false>, dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32, ws);
-  }
-#define ANR_BWD_LAUNCH(FASTV, ROWSV) \
-  hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, FASTV, ROWSV, BF>), grid, block, 0, st, a, target, \
-                     gm.tpw, ws)
-  if (a.rows) {
-    if (fast) ANR_BWD_LAUNCH(true, true); else ANR_BWD_LAUNCH(false, true);
-  } else {
-    if (fast) ANR_BWD_LAUNCH(true, false); else ANR_BWD_LAUNCH(false, false);
-  }
-#undef ANR_BWD_LAUNCH
-  return 0;
-}
-
-// S > 1 density outputs: the f32 dense-row forward (both forms), the density kernel and
-// the build-numerics backward; same grids and launch rules as run(), from the S kernels' own
-// occupancy. The callers refuse every other form before they get here.
-template <int W, int NHD, bool BF, int S>
-static int run_s(int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
-  static_assert(S >= 2 && S <= 4, "run(): S = 1");
-  using N = Net<W, NHD, S>;
-  const int waves = 4;
-  if (a.rows || a.color_h || a.d_color_h || a.loss_scale > 0.0f) return 1;
-  if (op == 1) {
-    const int64_t tiles = (a.M + 15) / 16;
-    const void* fn =
-        reinterpret_cast<const void*>(&fwd_kernel<W, NHD, false, BF, false, false, S>);
-    const int64_t blocks =
-        persistent_blocks((tiles + waves - 1) / waves, blocks_per_cu(fn, 64 * waves));
-    // S <= 4 <= color_stride: the sigma byte offsets stay below the colour rows' bound
-    const bool ut = g_fwd_ut && a.n_per_ray % 16 == 0 && a.n_out == 4 &&
-                    (a.color_stride & 3) == 0 && a.M * a.color_stride * 4 < (int64_t{1} << 31);
-    if (ut)
-      hipLaunchKernelGGL((fwd_kernel<W, NHD, false, BF, true, false, S>), dim3(blocks),
-                         dim3(64 * waves), 0, st, a);
-    else
-      hipLaunchKernelGGL((fwd_kernel<W, NHD, false, BF, false, false, S>), dim3(blocks),
-                         dim3(64 * waves), 0, st, a);
-    return 0;
-  }
-  if (op == 3) {
-    const int64_t tiles = (a.M + 15) / 16;
-    const int64_t blocks = persistent_blocks((tiles + waves - 1) / waves, 8);
-    hipLaunchKernelGGL((density_kernel<W, NHD, BF, S>), dim3(blocks), dim3(64 * waves), 0, st, a);
-    return 0;
-  }
-  const bool fast = a.n_out == 4 && (a.d_color_stride & 3) == 0 && a.d_sigma != nullptr;
-  const size_t lds = static_cast<size_t>(N::n_packed) * 2 + sizeof(float) * (N::NPOS + N::NDIR);
-  if (lds > 160 * 1024) return 1;
+  if (lds > 160 * 1024) return Plan::no_kernel;
   const BwdGeom gm = bwd_geom<W, NHD, BF, S>(a.M, fast);
   if (!BF && (ws == nullptr || ws_bytes < static_cast<int64_t>(sizeof(float)) * gm.nw))
-    return 2;
-  const float target = ldexpf(1.0f, g_target_log2);
-  const dim3 grid(static_cast<unsigned>(gm.blocks)), block(64 * waves);
-  if (!BF)
-    hipLaunchKernelGGL((absmax_kernel<false, S>), dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32,
-                       ws);
-  if (fast)
-    hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>), grid, block, 0, st,
-                       a, target, gm.tpw, ws);
-  else
-    hipLaunchKernelGGL((bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>), grid, block, 0, st,
-                       a, target, gm.tpw, ws);
-  return 0;
-}
-
-template <int W, int NHD>
-static void launch_pack(const float* pp, const float* pd, _Float16* out, bool bf, int ns,
-                        hipStream_t st) {
-  using N = Net<W, NHD>;
-  const dim3 grid((N::n_packed + 255) / 256);
-#define ANR_PACK(BFV, SV) \
-  hipLaunchKernelGGL((pack_kernel<W, NHD, BFV, SV>), grid, dim3(256), 0, st, pp, pd, out)
-  switch (ns * 2 + (bf ? 1 : 0)) {
-    case 2: ANR_PACK(false, 1); break;
-    case 3: ANR_PACK(true, 1); break;
-    case 4: ANR_PACK(false, 2); break;
-    case 5: ANR_PACK(true, 2); break;
-    case 6: ANR_PACK(false, 3); break;
-    case 7: ANR_PACK(true, 3); break;
-    case 8: ANR_PACK(false, 4); break;
-    case 9: ANR_PACK(true, 4); break;
+    return Plan::workspace;
+  void (*amax)(Args, int64_t, float*) = absmax_kernel<false, S>;
+  BwdKernel k = fast ? bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>
+                     : bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>;
+  if constexpr (S == 1) {
+    if (a.rows) {
+      amax = absmax_kernel<true>;
+      k = fast ? bwd_rt_kernel<W, NHD, true, true, BF> : bwd_rt_kernel<W, NHD, false, true, BF>;
+    }
   }
-#undef ANR_PACK
+  if (!BF) hipLaunchKernelGGL(amax, dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32, ws);
+  launch_bwd(k, gm.blocks, a, ldexpf(1.0f, g_target_log2), gm.tpw, ws, st);
+  return Plan::ok;
 }
 
 // Density outputs S of a dir network: its 20 - S inputs are SH2 (4) and pos_out[S:16]
 // (multi_band_extinction: S = num_bands; 1 otherwise). Meaningful once variant() != 0.
 static int n_sigma(const anr_mlp_desc* dir) { return 20 - dir->n_input; }
 
-// (W, NHD) of a supported pos/dir pair, or 0
+// 10 W + NHD of a supported pos/dir pair (with_net's list), or 0
 static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
   if (!pos || !dir) return 0;
   if (pos->n_input != 32 || pos->n_input_padded != 32 || pos->n_output != 16 ||
@@ -2558,123 +2522,37 @@ static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
 }
 
 // fused hash-grid + field forward: a persistent grid of HF_WAVES-wavefront blocks, as many
-// as fit on the chip at once (the occupancy query), each wavefront walking 64-sample
-// segments grid-stride
+// as the device holds at once, each wavefront walking 64-sample segments grid-stride
 constexpr int HF_WAVES = 8;
 // register cap of the fused forward: 6 waves per SIMD. It runs without run-leader gathers
 // (DEDUP 0): with them it measured 0.74-0.79 ms at caps of 4, 5 and 6 against 0.64-0.65 ms
 // without (profiles/r06_hash_field_fwd_variants.log).
 constexpr int HF_OCC = 6;
 template <int W, int NHD, bool BF>
-static int run_hf(const Args& a, const HashArgs& h, hipStream_t st) {
-  const void* fn = reinterpret_cast<const void*>(&hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>);
+static Plan plan_hf(const Args& a, const HashArgs& h, hipStream_t st) {
+  const auto k = hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>;
   const int64_t n_super = (a.M + 63) / 64;
-  const int64_t blocks = persistent_blocks((n_super + HF_WAVES - 1) / HF_WAVES,
-                                           blocks_per_cu(fn, 64 * HF_WAVES));
-  hipLaunchKernelGGL((hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>), dim3(blocks),
-                     dim3(64 * HF_WAVES), 0, st, a, h);
-  return 0;
-}
-template <bool BF>
-static int dispatch_hf_t(int v, const Args& a, const HashArgs& h, hipStream_t st) {
-  switch (v) {
-    case 321: return run_hf<32, 1, BF>(a, h, st);
-    case 322: return run_hf<32, 2, BF>(a, h, st);
-    case 641: return run_hf<64, 1, BF>(a, h, st);
-    case 642: return run_hf<64, 2, BF>(a, h, st);
-  }
-  return 1;
+  const int64_t blocks =
+      persistent_blocks((n_super + HF_WAVES - 1) / HF_WAVES,
+                        resident_blocks(reinterpret_cast<const void*>(k), 64 * HF_WAVES));
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * HF_WAVES), 0, st, a, h);
+  return Plan::ok;
 }
 
-// forward-only render: a persistent grid of RN_WAVES-wavefront blocks, a wavefront per ray.
-// The grid is what the current device holds at once: its CU count times the occupancy
-// query's blocks per CU, both asked per device and kept (no allocation, no synchronisation).
+// forward-only render: a persistent grid of RN_WAVES-wavefront blocks, as many as the device
+// holds at once, a wavefront per ray
 constexpr int RN_WAVES = 8;
 constexpr int RN_OCC = 4;
-static int64_t render_grid(const void* fn, int threads, int64_t work_blocks) {
-  static std::mutex mu;
-  static std::unordered_map<uint64_t, int64_t> cache;  // (device, kernel) -> resident blocks
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  int64_t cap;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    int64_t& c = cache[(static_cast<uint64_t>(dev) << 56) ^ reinterpret_cast<uintptr_t>(fn)];
-    if (c == 0) {
-      int cus = 0, per_cu = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-          cus < 1)
-        cus = 1;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess ||
-          per_cu < 1)
-        per_cu = 1;
-      c = static_cast<int64_t>(cus) * per_cu;
-    }
-    cap = c;
-  }
-  const int64_t blocks = work_blocks < cap ? work_blocks : cap;
-  return blocks < 1 ? 1 : blocks;
-}
 template <int W, int NHD, bool BF, bool REF>
-static int run_render(const Args& a, const HashArgs& h, const RenderArgs& r, hipStream_t st) {
-  const void* fn =
-      reinterpret_cast<const void*>(&render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>);
-  const int64_t blocks = render_grid(fn, 64 * RN_WAVES, (r.B + RN_WAVES - 1) / RN_WAVES);
-  hipLaunchKernelGGL((render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>), dim3(blocks),
-                     dim3(64 * RN_WAVES), 0, st, a, h, r);
-  return 0;
-}
-template <bool BF, bool REF>
-static int dispatch_render(int v, const Args& a, const HashArgs& h, const RenderArgs& r,
-                           hipStream_t st) {
-  switch (v) {
-    case 321: return run_render<32, 1, BF, REF>(a, h, r, st);
-    case 322: return run_render<32, 2, BF, REF>(a, h, r, st);
-    case 641: return run_render<64, 1, BF, REF>(a, h, r, st);
-    case 642: return run_render<64, 2, BF, REF>(a, h, r, st);
-  }
-  return 1;
+static Plan plan_render(const Args& a, const HashArgs& h, const RenderArgs& r, hipStream_t st) {
+  const auto k = render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>;
+  const int64_t blocks =
+      persistent_blocks((r.B + RN_WAVES - 1) / RN_WAVES,
+                        resident_blocks(reinterpret_cast<const void*>(k), 64 * RN_WAVES));
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * RN_WAVES), 0, st, a, h, r);
+  return Plan::ok;
 }
 
-template <bool BF>
-static int dispatch_t(int v, int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
-  switch (v) {
-    case 321: return run<32, 1, BF>(op, a, ws, ws_bytes, st);
-    case 322: return run<32, 2, BF>(op, a, ws, ws_bytes, st);
-    case 641: return run<64, 1, BF>(op, a, ws, ws_bytes, st);
-    case 642: return run<64, 2, BF>(op, a, ws, ws_bytes, st);
-  }
-  return 1;
-}
-template <bool BF, int S>
-static int dispatch_s(int v, int op, const Args& a, float* ws, int64_t ws_bytes, hipStream_t st) {
-  switch (v) {
-    case 321: return run_s<32, 1, BF, S>(op, a, ws, ws_bytes, st);
-    case 322: return run_s<32, 2, BF, S>(op, a, ws, ws_bytes, st);
-    case 641: return run_s<64, 1, BF, S>(op, a, ws, ws_bytes, st);
-    case 642: return run_s<64, 2, BF, S>(op, a, ws, ws_bytes, st);
-  }
-  return 1;
-}
-// ns: the pair's density outputs (n_sigma)
-static int dispatch(int v, int ns, bool bf, int op, const Args& a, float* ws, int64_t ws_bytes,
-                    hipStream_t st) {
-  switch (ns) {
-    case 1:
-      return bf ? dispatch_t<true>(v, op, a, ws, ws_bytes, st)
-                : dispatch_t<false>(v, op, a, ws, ws_bytes, st);
-    case 2:
-      return bf ? dispatch_s<true, 2>(v, op, a, ws, ws_bytes, st)
-                : dispatch_s<false, 2>(v, op, a, ws, ws_bytes, st);
-    case 3:
-      return bf ? dispatch_s<true, 3>(v, op, a, ws, ws_bytes, st)
-                : dispatch_s<false, 3>(v, op, a, ws, ws_bytes, st);
-    case 4:
-      return bf ? dispatch_s<true, 4>(v, op, a, ws, ws_bytes, st)
-                : dispatch_s<false, 4>(v, op, a, ws, ws_bytes, st);
-  }
-  return 1;
-}
 // Entry points that stay at one density output answer a multi-band pair with this.
 static bool multi_band(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
   return variant(pos, dir) != 0 && n_sigma(dir) > 1;
@@ -2695,37 +2573,19 @@ extern "C" int anr_ingp_field_supported(const anr_mlp_desc* pos, const anr_mlp_d
 }
 
 extern "C" int64_t anr_ingp_field_packed_size(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
-  switch (variant(pos, dir)) {
-    case 321: return Net<32, 1>::n_packed;
-    case 322: return Net<32, 2>::n_packed;
-    case 641: return Net<64, 1>::n_packed;
-    case 642: return Net<64, 2>::n_packed;
-  }
-  return 0;
+  return with_net(variant(pos, dir), int64_t{0},
+                  [](auto net) { return int64_t{Net<net.W, net.NHD>::n_packed}; });
 }
 
 extern "C" int64_t anr_ingp_field_bwd_workspace_bytes(const anr_mlp_desc* pos,
                                                       const anr_mlp_desc* dir,
                                                       int32_t mma_dtype, int64_t M) {
-  if (mma_dtype == ANR_BF16) return 0;
   const int v = variant(pos, dir);
   if (v == 0) return 0;
-#define ANR_WS(SV)                                            \
-  switch (v) {                                                \
-    case 321: return bwd_workspace<32, 1, false, SV>(M);      \
-    case 322: return bwd_workspace<32, 2, false, SV>(M);      \
-    case 641: return bwd_workspace<64, 1, false, SV>(M);      \
-    case 642: return bwd_workspace<64, 2, false, SV>(M);      \
-  }                                                           \
-  return 0
-  switch (n_sigma(dir)) {
-    case 1: ANR_WS(1);
-    case 2: ANR_WS(2);
-    case 3: ANR_WS(3);
-    case 4: ANR_WS(4);
-  }
-#undef ANR_WS
-  return 0;
+  return with_variant(v, n_sigma(dir), mma_dtype == ANR_BF16, int64_t{0},
+                      [&](auto net, auto s, auto bf) {
+                        return bwd_workspace<net.W, net.NHD, bf(), s()>(M);
+                      });
 }
 
 extern "C" int anr_ingp_field_force_fwd(int32_t mode) {
@@ -2741,6 +2601,11 @@ extern "C" int anr_ingp_field_set_grad_scale(int32_t log2_target) {
 }
 
 static bool mma_ok(int32_t t) { return t == ANR_F16 || t == ANR_BF16; }
+static bool aligned(const void* p, uintptr_t bytes) {
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+// S > 1: a row's S densities leave (arrive) as one access of 4 S bytes, 4 for S = 3
+static int band_align(int ns) { return ns == 3 ? 4 : 4 * ns; }
 
 // enc_stride >= 32 (multiple of 8): row layout; enc_stride = -P: level-quad planes of P
 // f16 elements each (P >= 8 M, multiple of 8), as anr_hashgrid_fwd_planes writes them
@@ -2766,41 +2631,41 @@ extern "C" int anr_ingp_field_pack(const anr_mlp_desc* pos, const anr_mlp_desc* 
   ANR_CHECK_ARG(v != 0, "anr_ingp_field_pack: unsupported pos/dir MLP pair");
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_pack: mma_dtype must be ANR_F16 or ANR_BF16");
   ANR_CHECK_ARG(pos_params && dir_params && packed, "anr_ingp_field_pack: null pointer");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  _Float16* out = static_cast<_Float16*>(packed);
-  const bool bf = mma_dtype == ANR_BF16;
-  switch (v) {
-    case 321: launch_pack<32, 1>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
-    case 322: launch_pack<32, 2>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
-    case 641: launch_pack<64, 1>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
-    case 642: launch_pack<64, 2>(pos_params, dir_params, out, bf, n_sigma(dir), st); break;
-  }
+  with_variant(v, n_sigma(dir), mma_dtype == ANR_BF16, 0, [&](auto net, auto s, auto bf) {
+    hipLaunchKernelGGL((pack_kernel<net.W, net.NHD, bf(), s()>),
+                       dim3((Net<net.W, net.NHD>::n_packed + 255) / 256), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), pos_params, dir_params,
+                       static_cast<_Float16*>(packed));
+    return 0;
+  });
   ANR_CHECK_LAUNCH("anr_ingp_field_pack");
   return ANR_OK;
 }
 
+// what only some forward entries pass; zero: absent
+struct FwdForm {
+  const int32_t* rows;  // anr_ingp_field_fwd_rows
+  bool half_out;        // anr_ingp_field_fwd_h: sigma and color are f16
+};
+
 static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t mma_dtype,
                      const void* packed, const void* enc, int64_t enc_stride, const float* dirs,
-                     int64_t n_per_ray, int64_t M, const int32_t* rows, void* sigma,
-                     void* color, int64_t color_stride, anr_stream_t stream,
-                     bool half_out = false) {
+                     int64_t n_per_ray, int64_t M, void* sigma, void* color,
+                     int64_t color_stride, anr_stream_t stream, const FwdForm& f) {
   const int v = variant(pos, dir);
   ANR_CHECK_ARG(v != 0, "anr_ingp_field_fwd: unsupported pos/dir MLP pair");
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_fwd: mma_dtype must be ANR_F16 or ANR_BF16");
   ANR_CHECK_ARG(M >= 0 && M < (1LL << 31), "anr_ingp_field_fwd: bad M");
   if (M == 0) return ANR_OK;
   const int ns = n_sigma(dir);
-  if (ns > 1 && (half_out || rows))
-    return refuse_bands(half_out ? "anr_ingp_field_fwd_h" : "anr_ingp_field_fwd_rows");
+  if (ns > 1 && (f.half_out || f.rows))
+    return refuse_bands(f.half_out ? "anr_ingp_field_fwd_h" : "anr_ingp_field_fwd_rows");
   ANR_CHECK_ARG(packed && enc && dirs && sigma && color, "anr_ingp_field_fwd: null pointer");
-  // S > 1: a row's S densities leave as one store
-  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
-                "anr_ingp_field_fwd: sigma (M, %d) must be %d-byte aligned", ns,
-                ns == 3 ? 4 : 4 * ns);
+  ANR_CHECK_ARG(ns == 1 || aligned(sigma, band_align(ns)),
+                "anr_ingp_field_fwd: sigma (M, %d) must be %d-byte aligned", ns, band_align(ns));
   ANR_CHECK_ARG(n_per_ray >= 1 && n_per_ray < (1LL << 31) && color_stride >= dir->n_output,
                 "anr_ingp_field_fwd: bad shape/stride");
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(enc) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
+  ANR_CHECK_ARG(aligned(enc, 16) && aligned(packed, 16),
                 "anr_ingp_field_fwd: enc/packed must be 16-byte aligned");
   Args a{};
   a.packed = static_cast<const _Float16*>(packed);
@@ -2811,10 +2676,10 @@ static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   a.n_per_ray = static_cast<uint32_t>(n_per_ray);
   a.M = M;
   a.n_out = dir->n_output;
-  if (half_out) {
-    ANR_CHECK_ARG(rows == nullptr, "anr_ingp_field_fwd_h: dense rows only");
+  if (f.half_out) {
+    ANR_CHECK_ARG(f.rows == nullptr, "anr_ingp_field_fwd_h: dense rows only");
     // 4-wide colour rows go out as one 8-byte store
-    ANR_CHECK_ARG((color_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(color) & 7) == 0,
+    ANR_CHECK_ARG((color_stride & 3) != 0 || aligned(color, 8),
                   "anr_ingp_field_fwd_h: color must be 8-byte aligned");
     a.sigma_h = static_cast<_Float16*>(sigma);
     a.color_h = static_cast<_Float16*>(color);
@@ -2823,12 +2688,43 @@ static int field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
     a.color = static_cast<float*>(color);
   }
   a.color_stride = color_stride;
-  a.rows = rows;
-  ANR_CHECK_ARG(dispatch(v, ns, mma_dtype == ANR_BF16, 1, a, nullptr, 0,
-                         reinterpret_cast<hipStream_t>(stream)) == 0,
-                "anr_ingp_field_fwd: no kernel for this shape");
+  a.rows = f.rows;
+  const Plan rc = with_variant(v, ns, mma_dtype == ANR_BF16, Plan::no_kernel,
+                               [&](auto net, auto s, auto bf) {
+                                 return plan_fwd<net.W, net.NHD, bf(), s()>(
+                                     a, reinterpret_cast<hipStream_t>(stream));
+                               });
+  ANR_CHECK_ARG(rc == Plan::ok, "anr_ingp_field_fwd: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_field_fwd");
   return ANR_OK;
+}
+
+// The configuration the hash+field forward and the render take (v: variant() of the pair).
+static bool hash_field_config(const anr_hashgrid_desc* grid, int32_t table_dtype, int v,
+                              const anr_mlp_desc* dir, int32_t mma_dtype, int64_t n_per_ray) {
+  return v != 0 && mma_ok(mma_dtype) && table_dtype == ANR_F16 && grid->n_dims == 3 &&
+         grid->n_features == 2 && grid->n_levels == 16 && dir->n_output == 4 && n_per_ray >= 64 &&
+         n_per_ray % 64 == 0;
+}
+// Their shared arguments: M samples x of rays of n_per_ray, the table and the field. False
+// when the byte range of x (with a segment's overrun) or of the table reaches 2^31.
+static bool set_hash_field(Args& a, HashArgs& h, const ::anr::GridLevels& G, const float* x,
+                           int64_t M, const void* table, const void* packed, const float* dirs,
+                           int64_t n_per_ray) {
+  const int64_t lim = int64_t(1) << 31;
+  const int64_t t_bytes = static_cast<int64_t>(G.offset[15] + G.size[15]) * 4;
+  if ((M + 64) * 12 >= lim || t_bytes >= lim) return false;
+  a.packed = static_cast<const _Float16*>(packed);
+  a.dirs = dirs;
+  a.n_per_ray = static_cast<uint32_t>(n_per_ray);
+  a.M = M;
+  a.n_out = 4;
+  h.G = G;
+  h.x = x;
+  h.x_bytes = static_cast<uint32_t>(M * 12);
+  h.table = static_cast<const __half*>(table);
+  h.table_bytes = static_cast<uint32_t>(t_bytes);
+  return true;
 }
 
 extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const float* x, int64_t M,
@@ -2843,9 +2739,8 @@ extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const floa
   if (v != 0 && n_sigma(dir) > 1) return refuse_bands("anr_ingp_hash_field_fwd");
   ANR_CHECK_ARG(grid && x && table && planes && packed && dirs && sigma && color,
                 "anr_ingp_hash_field_fwd: null pointer");
-  if (v == 0 || !mma_ok(mma_dtype) || table_dtype != ANR_F16 || grid->n_dims != 3 ||
-      grid->n_features != 2 || grid->n_levels != 16 || dir->n_output != 4 ||
-      n_per_ray < 64 || n_per_ray % 64 != 0 || color_stride < 4 || color_stride % 4 != 0) {
+  if (!hash_field_config(grid, table_dtype, v, dir, mma_dtype, n_per_ray) || color_stride < 4 ||
+      color_stride % 4 != 0) {
     ::anr::set_error("anr_ingp_hash_field_fwd: unsupported configuration (3-D f16 grid of 16 "
                      "levels x 2 features, a supported field pair with 4 colour outputs, "
                      "samples per ray a multiple of 64, colour rows 16-byte aligned)");
@@ -2853,40 +2748,29 @@ extern "C" int anr_ingp_hash_field_fwd(const anr_hashgrid_desc* grid, const floa
   }
   ANR_CHECK_ARG(M > 0 && plane_stride >= 8 * M && plane_stride % 8 == 0,
                 "anr_ingp_hash_field_fwd: bad M / plane_stride (>= 8 M, multiple of 8)");
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(planes) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(packed) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(color) & 15) == 0,
+  ANR_CHECK_ARG(aligned(planes, 16) && aligned(packed, 16) && aligned(color, 16),
                 "anr_ingp_hash_field_fwd: planes / packed / color must be 16-byte aligned");
   ::anr::GridLevels G;
   ANR_CHECK_ARG(::anr::make_levels(grid, &G), "anr_ingp_hash_field_fwd: descriptor not initialised");
   const int64_t lim = int64_t(1) << 31;
-  const int64_t t_bytes = static_cast<int64_t>(G.offset[15] + G.size[15]) * 4;
   const int64_t o_bytes = (3 * plane_stride + 8 * M) * 2;
-  ANR_CHECK_ARG((M + 64) * 12 < lim && t_bytes < lim && o_bytes < lim && plane_stride * 2 < lim &&
-                    M * color_stride * 4 < lim,
-                "anr_ingp_hash_field_fwd: byte ranges must stay below 2^31");
   Args a{};
-  a.packed = static_cast<const _Float16*>(packed);
-  a.dirs = dirs;
-  a.n_per_ray = static_cast<uint32_t>(n_per_ray);
-  a.M = M;
-  a.n_out = dir->n_output;
+  HashArgs h{};
+  ANR_CHECK_ARG(set_hash_field(a, h, G, x, M, table, packed, dirs, n_per_ray) && o_bytes < lim &&
+                    plane_stride * 2 < lim && M * color_stride * 4 < lim,
+                "anr_ingp_hash_field_fwd: byte ranges must stay below 2^31");
   a.sigma = sigma;
   a.color = color;
   a.color_stride = color_stride;
-  HashArgs h{};
-  h.G = G;
-  h.x = x;
-  h.x_bytes = static_cast<uint32_t>(M * 12);
-  h.table = static_cast<const __half*>(table);
-  h.table_bytes = static_cast<uint32_t>(t_bytes);
   h.planes = static_cast<_Float16*>(planes);
   h.plane_bytes = static_cast<uint32_t>(plane_stride * 2);
   h.out_bytes = static_cast<uint32_t>(o_bytes);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int rc = mma_dtype == ANR_BF16 ? dispatch_hf_t<true>(v, a, h, st)
-                                       : dispatch_hf_t<false>(v, a, h, st);
-  ANR_CHECK_ARG(rc == 0, "anr_ingp_hash_field_fwd: no kernel for this shape");
+  const Plan rc = with_net(v, Plan::no_kernel, [&](auto net) {
+    return with_bool(mma_dtype == ANR_BF16, [&](auto bf) {
+      return plan_hf<net.W, net.NHD, bf()>(a, h, reinterpret_cast<hipStream_t>(stream));
+    });
+  });
+  ANR_CHECK_ARG(rc == Plan::ok, "anr_ingp_hash_field_fwd: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_hash_field_fwd");
   return ANR_OK;
 }
@@ -2905,40 +2789,26 @@ extern "C" int anr_ingp_render(const anr_hashgrid_desc* grid, const float* coord
                 "anr_ingp_render: numerics must be ANR_RENDER_BUILD or ANR_RENDER_REFERENCE");
   const int v = variant(pos, dir);
   if (v != 0 && n_sigma(dir) > 1) return refuse_bands("anr_ingp_render");
-  if (v == 0 || !mma_ok(mma_dtype) || table_dtype != ANR_F16 || grid->n_dims != 3 ||
-      grid->n_features != 2 || grid->n_levels != 16 || dir->n_output != 4 || n_per_ray < 64 ||
-      n_per_ray % 64 != 0) {
+  if (!hash_field_config(grid, table_dtype, v, dir, mma_dtype, n_per_ray)) {
     ::anr::set_error("anr_ingp_render: unsupported configuration (3-D f16 grid of 16 levels x 2 "
                      "features, a supported field pair with one density and 4 colour outputs, "
                      "f16 or bf16 MFMA, samples per ray a positive multiple of 64)");
     return ANR_E_UNSUPPORTED;
   }
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0) {
+  if (!aligned(packed, 16)) {
     ::anr::set_error("anr_ingp_render: unsupported: packed weights must be 16-byte aligned");
     return ANR_E_UNSUPPORTED;
   }
   ::anr::GridLevels G;
   ANR_CHECK_ARG(::anr::make_levels(grid, &G), "anr_ingp_render: descriptor not initialised");
   const int64_t lim = int64_t(1) << 31;
-  const int64_t t_bytes = static_cast<int64_t>(G.offset[15] + G.size[15]) * 4;
-  if (n_per_ray >= lim || B >= lim / n_per_ray || (B * n_per_ray + 64) * 12 >= lim ||
-      t_bytes >= lim) {
+  Args a{};
+  HashArgs h{};
+  if (n_per_ray >= lim || B >= lim / n_per_ray ||
+      !set_hash_field(a, h, G, coords, B * n_per_ray, table, packed, dirs, n_per_ray)) {
     ::anr::set_error("anr_ingp_render: unsupported: byte ranges must stay below 2^31");
     return ANR_E_UNSUPPORTED;
   }
-  const int64_t M = B * n_per_ray;
-  Args a{};
-  a.packed = static_cast<const _Float16*>(packed);
-  a.dirs = dirs;
-  a.n_per_ray = static_cast<uint32_t>(n_per_ray);
-  a.M = M;
-  a.n_out = 4;
-  HashArgs h{};
-  h.G = G;
-  h.x = coords;
-  h.x_bytes = static_cast<uint32_t>(M * 12);
-  h.table = static_cast<const __half*>(table);
-  h.table_bytes = static_cast<uint32_t>(t_bytes);
   RenderArgs r{};
   r.z = z;
   r.zs = z_scale;
@@ -2947,51 +2817,60 @@ extern "C" int anr_ingp_render(const anr_hashgrid_desc* grid, const float* coord
   r.atmo = atmo;
   r.surf = surf;
   r.B = B;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool bf = mma_dtype == ANR_BF16;
-  const int rc = numerics == ANR_RENDER_REFERENCE
-                     ? (bf ? dispatch_render<true, true>(v, a, h, r, st)
-                           : dispatch_render<false, true>(v, a, h, r, st))
-                     : (bf ? dispatch_render<true, false>(v, a, h, r, st)
-                           : dispatch_render<false, false>(v, a, h, r, st));
-  ANR_CHECK_ARG(rc == 0, "anr_ingp_render: no kernel for this shape");
+  const Plan rc = with_net(v, Plan::no_kernel, [&](auto net) {
+    return with_bool(mma_dtype == ANR_BF16, [&](auto bf) {
+      return with_bool(numerics == ANR_RENDER_REFERENCE, [&](auto ref) {
+        return plan_render<net.W, net.NHD, bf(), ref()>(a, h, r,
+                                                        reinterpret_cast<hipStream_t>(stream));
+      });
+    });
+  });
+  ANR_CHECK_ARG(rc == Plan::ok, "anr_ingp_render: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_render");
   return ANR_OK;
 }
 
+// what only some backward entries pass; zero: absent
+struct BwdForm {
+  const int32_t* rows;      // anr_ingp_field_bwd_rows
+  float loss_scale;         // > 0: reference numerics (the ref16 entries)
+  uint8_t* tile_nz;         // _ref16_tiles
+  void* d_enc_h;            // _ref16_rows: dL/denc as f16 rows (d_enc null), with
+  uint32_t* row_nz;         //   the row bits
+  void* tiles_ws;           //   and the pos / list passes' workspace (nullable)
+  bool half_grad;           // _ref16_rows_h: d_sigma and d_color are f16
+  void* workspace;          // build numerics: the wavefronts' gradient maxima
+  int64_t workspace_bytes;
+};
+
 static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t mma_dtype,
                      const void* packed, const void* enc, int64_t enc_stride, const float* dirs,
-                     int64_t n_per_ray, int64_t M, const int32_t* rows, const void* d_sigma,
-                     const void* d_color, int64_t d_color_stride, float* d_enc,
-                     int64_t d_enc_stride, float* g_pos, float* g_dir, void* workspace,
-                     int64_t workspace_bytes, anr_stream_t stream, float loss_scale = 0.0f,
-                     uint8_t* tile_nz = nullptr, void* d_enc_h = nullptr,
-                     uint32_t* row_nz = nullptr, void* tiles_ws = nullptr,
-                     bool half_grad = false) {
+                     int64_t n_per_ray, int64_t M, const void* d_sigma, const void* d_color,
+                     int64_t d_color_stride, float* d_enc, int64_t d_enc_stride, float* g_pos,
+                     float* g_dir, anr_stream_t stream, const BwdForm& f) {
   const int v = variant(pos, dir);
   ANR_CHECK_ARG(v != 0, "anr_ingp_field_bwd: unsupported pos/dir MLP pair");
-  ANR_CHECK_ARG(loss_scale == 0.0f || (loss_scale > 0.0f && mma_dtype == ANR_F16 && rows == nullptr),
+  ANR_CHECK_ARG(f.loss_scale == 0.0f ||
+                    (f.loss_scale > 0.0f && mma_dtype == ANR_F16 && f.rows == nullptr),
                 "anr_ingp_field_bwd: reference numerics need f16 MMA and dense rows");
   ANR_CHECK_ARG(mma_ok(mma_dtype), "anr_ingp_field_bwd: mma_dtype must be ANR_F16 or ANR_BF16");
   ANR_CHECK_ARG(M >= 0 && M < (1LL << 31), "anr_ingp_field_bwd: bad M");
   if (M == 0) return ANR_OK;
   const int ns = n_sigma(dir);
-  if (ns > 1 && (loss_scale > 0.0f || rows))
-    return refuse_bands(rows ? "anr_ingp_field_bwd_rows" : "anr_ingp_field_bwd_ref16");
-  ANR_CHECK_ARG(packed && enc && dirs && d_color && (d_enc || (d_enc_h && row_nz)) && g_pos && g_dir,
+  if (ns > 1 && (f.loss_scale > 0.0f || f.rows))
+    return refuse_bands(f.rows ? "anr_ingp_field_bwd_rows" : "anr_ingp_field_bwd_ref16");
+  ANR_CHECK_ARG(packed && enc && dirs && d_color && (d_enc || (f.d_enc_h && f.row_nz)) && g_pos &&
+                    g_dir,
                 "anr_ingp_field_bwd: null pointer");
-  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(d_sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
-                "anr_ingp_field_bwd: d_sigma (M, %d) must be %d-byte aligned", ns,
-                ns == 3 ? 4 : 4 * ns);
-  ANR_CHECK_ARG(d_enc_h == nullptr || loss_scale > 0.0f,
+  ANR_CHECK_ARG(ns == 1 || aligned(d_sigma, band_align(ns)),
+                "anr_ingp_field_bwd: d_sigma (M, %d) must be %d-byte aligned", ns, band_align(ns));
+  ANR_CHECK_ARG(f.d_enc_h == nullptr || f.loss_scale > 0.0f,
                 "anr_ingp_field_bwd: f16 rows and row bits are reference numerics only");
   ANR_CHECK_ARG(n_per_ray >= 1 && n_per_ray < (1LL << 31) && d_color_stride >= dir->n_output &&
                     d_enc_stride >= 32 && d_enc_stride % 4 == 0,
                 "anr_ingp_field_bwd: bad shape/stride");
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(enc) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(packed) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d_enc) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(d_enc_h) & 7) == 0,
+  ANR_CHECK_ARG(aligned(enc, 16) && aligned(packed, 16) && aligned(d_enc, 16) &&
+                    aligned(f.d_enc_h, 8),
                 "anr_ingp_field_bwd: enc/packed/d_enc must be 16-byte aligned (f16 rows: 8)");
   Args a{};
   a.packed = static_cast<const _Float16*>(packed);
@@ -3002,9 +2881,9 @@ static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   a.n_per_ray = static_cast<uint32_t>(n_per_ray);
   a.M = M;
   a.n_out = dir->n_output;
-  if (half_grad) {  // f16 dL/dsigma, dL/dcolor: 4-wide rows are read as one 8-byte load
-    ANR_CHECK_ARG(d_enc_h != nullptr, "anr_ingp_field_bwd: f16 gradients need the f16-rows form");
-    ANR_CHECK_ARG((d_color_stride & 3) != 0 || (reinterpret_cast<uintptr_t>(d_color) & 7) == 0,
+  if (f.half_grad) {  // f16 dL/dsigma, dL/dcolor: 4-wide rows are read as one 8-byte load
+    ANR_CHECK_ARG(f.d_enc_h != nullptr, "anr_ingp_field_bwd: f16 gradients need the f16-rows form");
+    ANR_CHECK_ARG((d_color_stride & 3) != 0 || aligned(d_color, 8),
                   "anr_ingp_field_bwd: f16 d_color must be 8-byte aligned");
     a.d_sigma_h = static_cast<const _Float16*>(d_sigma);
     a.d_color_h = static_cast<const _Float16*>(d_color);
@@ -3017,21 +2896,25 @@ static int field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* dir, int32_t m
   a.d_enc_stride = d_enc_stride;
   a.g_pos = g_pos;
   a.g_dir = g_dir;
-  a.rows = rows;
-  a.loss_scale = loss_scale;
-  a.tile_nz = tile_nz;
-  a.d_enc_h = static_cast<_Float16*>(d_enc_h);
-  a.row_nz = row_nz;
-  if (tiles_ws) {  // ref16_rows_workspace_bytes: the count, then one int32 per 32-row tile
-    a.tile_count = static_cast<uint32_t*>(tiles_ws);
-    a.tile_list = reinterpret_cast<int32_t*>(static_cast<char*>(tiles_ws) + 256);
+  a.rows = f.rows;
+  a.loss_scale = f.loss_scale;
+  a.tile_nz = f.tile_nz;
+  a.d_enc_h = static_cast<_Float16*>(f.d_enc_h);
+  a.row_nz = f.row_nz;
+  if (f.tiles_ws) {  // ref16_rows_workspace_bytes: the count, then one int32 per 32-row tile
+    a.tile_count = static_cast<uint32_t*>(f.tiles_ws);
+    a.tile_list = reinterpret_cast<int32_t*>(static_cast<char*>(f.tiles_ws) + 256);
   }
-  const int rc = dispatch(v, ns, mma_dtype == ANR_BF16, 2, a, static_cast<float*>(workspace),
-                          workspace_bytes, reinterpret_cast<hipStream_t>(stream));
-  ANR_CHECK_ARG(rc != 2,
+  const Plan rc = with_variant(v, ns, mma_dtype == ANR_BF16, Plan::no_kernel,
+                               [&](auto net, auto s, auto bf) {
+                                 return plan_bwd<net.W, net.NHD, bf(), s()>(
+                                     a, static_cast<float*>(f.workspace), f.workspace_bytes,
+                                     reinterpret_cast<hipStream_t>(stream));
+                               });
+  ANR_CHECK_ARG(rc != Plan::workspace,
                 "anr_ingp_field_bwd: workspace missing or smaller than "
                 "anr_ingp_field_bwd_workspace_bytes()");
-  ANR_CHECK_ARG(rc == 0, "anr_ingp_field_bwd: no kernel for this shape");
+  ANR_CHECK_ARG(rc == Plan::ok, "anr_ingp_field_bwd: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_field_bwd");
   return ANR_OK;
 }
@@ -3041,8 +2924,8 @@ extern "C" int anr_ingp_field_fwd(const anr_mlp_desc* pos, const anr_mlp_desc* d
                                   int64_t enc_stride, const float* dirs, int64_t n_per_ray,
                                   int64_t M, float* sigma, float* color, int64_t color_stride,
                                   anr_stream_t stream) {
-  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   sigma, color, color_stride, stream);
+  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, sigma, color,
+                   color_stride, stream, FwdForm{});
 }
 
 extern "C" int anr_ingp_field_fwd_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3050,8 +2933,10 @@ extern "C" int anr_ingp_field_fwd_h(const anr_mlp_desc* pos, const anr_mlp_desc*
                                     int64_t enc_stride, const float* dirs, int64_t n_per_ray,
                                     int64_t M, void* sigma, void* color, int64_t color_stride,
                                     anr_stream_t stream) {
-  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   sigma, color, color_stride, stream, true);
+  FwdForm f{};
+  f.half_out = true;
+  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, sigma, color,
+                   color_stride, stream, f);
 }
 
 extern "C" int anr_ingp_field_density(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3065,20 +2950,22 @@ extern "C" int anr_ingp_field_density(const anr_mlp_desc* pos, const anr_mlp_des
   if (M == 0) return ANR_OK;
   ANR_CHECK_ARG(packed && enc && sigma, "anr_ingp_field_density: null pointer");
   const int ns = n_sigma(dir);
-  ANR_CHECK_ARG(ns == 1 || (reinterpret_cast<uintptr_t>(sigma) & (ns == 3 ? 3 : 4 * ns - 1)) == 0,
+  ANR_CHECK_ARG(ns == 1 || aligned(sigma, band_align(ns)),
                 "anr_ingp_field_density: sigma (M, %d) must be %d-byte aligned", ns,
-                ns == 3 ? 4 : 4 * ns);
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(enc) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(packed) & 15) == 0,
+                band_align(ns));
+  ANR_CHECK_ARG(aligned(enc, 16) && aligned(packed, 16),
                 "anr_ingp_field_density: enc/packed must be 16-byte aligned");
   Args a{};
   a.packed = static_cast<const _Float16*>(packed);
   ANR_CHECK_ARG(set_enc(a, enc, enc_stride, M), "anr_ingp_field_density: bad enc_stride");
   a.M = M;
   a.sigma = sigma;
-  ANR_CHECK_ARG(dispatch(v, ns, mma_dtype == ANR_BF16, 3, a, nullptr, 0,
-                         reinterpret_cast<hipStream_t>(stream)) == 0,
-                "anr_ingp_field_density: no kernel for this shape");
+  const Plan rc = with_variant(v, ns, mma_dtype == ANR_BF16, Plan::no_kernel,
+                               [&](auto net, auto s, auto bf) {
+                                 return plan_density<net.W, net.NHD, bf(), s()>(
+                                     a, reinterpret_cast<hipStream_t>(stream));
+                               });
+  ANR_CHECK_ARG(rc == Plan::ok, "anr_ingp_field_density: no kernel for this shape");
   ANR_CHECK_LAUNCH("anr_ingp_field_density");
   return ANR_OK;
 }
@@ -3090,9 +2977,11 @@ extern "C" int anr_ingp_field_bwd(const anr_mlp_desc* pos, const anr_mlp_desc* d
                                   int64_t d_color_stride, float* d_enc, int64_t d_enc_stride,
                                   float* g_pos, float* g_dir, void* workspace,
                                   int64_t workspace_bytes, anr_stream_t stream) {
-  return field_bwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir,
-                   workspace, workspace_bytes, stream);
+  BwdForm f{};
+  f.workspace = workspace;
+  f.workspace_bytes = workspace_bytes;
+  return field_bwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, d_sigma,
+                   d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, stream, f);
 }
 
 extern "C" int anr_ingp_field_bwd_ref16(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3104,9 +2993,10 @@ extern "C" int anr_ingp_field_bwd_ref16(const anr_mlp_desc* pos, const anr_mlp_d
                                         float loss_scale, anr_stream_t stream) {
   if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16: loss_scale must be > 0");
-  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, nullptr,
-                   0, stream, loss_scale);
+  BwdForm f{};
+  f.loss_scale = loss_scale;
+  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, d_sigma,
+                   d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, stream, f);
 }
 
 extern "C" int anr_ingp_field_bwd_ref16_tiles(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3120,13 +3010,41 @@ extern "C" int anr_ingp_field_bwd_ref16_tiles(const anr_mlp_desc* pos, const anr
   if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_tiles");
   ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_tiles: loss_scale must be > 0");
   ANR_CHECK_ARG(tile_nz != nullptr, "anr_ingp_field_bwd_ref16_tiles: null tile_nz");
-  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, nullptr,
-                   0, stream, loss_scale, tile_nz);
+  BwdForm f{};
+  f.loss_scale = loss_scale;
+  f.tile_nz = tile_nz;
+  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, d_sigma,
+                   d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, stream, f);
 }
 
 extern "C" int64_t anr_ingp_field_bwd_ref16_rows_workspace_bytes(int64_t M) {
   return M <= 0 ? 0 : 256 + 4 * ((M + 31) / 32);
+}
+
+// anr_ingp_field_bwd_ref16_rows and _rows_h (half_grad: f16 d_sigma / d_color)
+static int field_bwd_ref16_rows(const char* entry, bool half_grad, const anr_mlp_desc* pos,
+                                const anr_mlp_desc* dir, const void* packed, const void* enc,
+                                int64_t enc_stride, const float* dirs, int64_t n_per_ray,
+                                int64_t M, const void* d_sigma, const void* d_color,
+                                int64_t d_color_stride, void* d_enc_h, int64_t d_enc_stride,
+                                float* g_pos, float* g_dir, float loss_scale, uint32_t* row_nz,
+                                void* workspace, int64_t workspace_bytes, anr_stream_t stream) {
+  if (M != 0 && multi_band(pos, dir)) return refuse_bands(entry);
+  ANR_CHECK_ARG(loss_scale > 0.0f, "%s: loss_scale must be > 0", entry);
+  ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr, "%s: null d_enc / row_nz", entry);
+  ANR_CHECK_ARG(workspace == nullptr ||
+                    workspace_bytes >= anr_ingp_field_bwd_ref16_rows_workspace_bytes(M),
+                "%s: workspace smaller than anr_ingp_field_bwd_ref16_rows_workspace_bytes()",
+                entry);
+  ANR_CHECK_ARG(aligned(workspace, 256), "%s: workspace must be 256-byte aligned", entry);
+  BwdForm f{};
+  f.loss_scale = loss_scale;
+  f.d_enc_h = d_enc_h;
+  f.row_nz = row_nz;
+  f.tiles_ws = workspace;
+  f.half_grad = half_grad;
+  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, d_sigma,
+                   d_color, d_color_stride, nullptr, d_enc_stride, g_pos, g_dir, stream, f);
 }
 
 extern "C" int anr_ingp_field_bwd_ref16_rows(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3138,19 +3056,10 @@ extern "C" int anr_ingp_field_bwd_ref16_rows(const anr_mlp_desc* pos, const anr_
                                              float* g_dir, float loss_scale, uint32_t* row_nz,
                                              void* workspace, int64_t workspace_bytes,
                                              anr_stream_t stream) {
-  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_rows");
-  ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_rows: loss_scale must be > 0");
-  ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr,
-                "anr_ingp_field_bwd_ref16_rows: null d_enc / row_nz");
-  ANR_CHECK_ARG(workspace == nullptr ||
-                    workspace_bytes >= anr_ingp_field_bwd_ref16_rows_workspace_bytes(M),
-                "anr_ingp_field_bwd_ref16_rows: workspace smaller than "
-                "anr_ingp_field_bwd_ref16_rows_workspace_bytes()");
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-                "anr_ingp_field_bwd_ref16_rows: workspace must be 256-byte aligned");
-  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   d_sigma, d_color, d_color_stride, nullptr, d_enc_stride, g_pos, g_dir, nullptr,
-                   0, stream, loss_scale, nullptr, d_enc_h, row_nz, workspace);
+  return field_bwd_ref16_rows("anr_ingp_field_bwd_ref16_rows", false, pos, dir, packed, enc,
+                              enc_stride, dirs, n_per_ray, M, d_sigma, d_color, d_color_stride,
+                              d_enc_h, d_enc_stride, g_pos, g_dir, loss_scale, row_nz, workspace,
+                              workspace_bytes, stream);
 }
 
 extern "C" int anr_ingp_field_bwd_ref16_rows_h(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3162,19 +3071,10 @@ extern "C" int anr_ingp_field_bwd_ref16_rows_h(const anr_mlp_desc* pos, const an
                                                float* g_dir, float loss_scale, uint32_t* row_nz,
                                                void* workspace, int64_t workspace_bytes,
                                                anr_stream_t stream) {
-  if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_ref16_rows_h");
-  ANR_CHECK_ARG(loss_scale > 0.0f, "anr_ingp_field_bwd_ref16_rows_h: loss_scale must be > 0");
-  ANR_CHECK_ARG(d_enc_h != nullptr && row_nz != nullptr,
-                "anr_ingp_field_bwd_ref16_rows_h: null d_enc / row_nz");
-  ANR_CHECK_ARG(workspace == nullptr ||
-                    workspace_bytes >= anr_ingp_field_bwd_ref16_rows_workspace_bytes(M),
-                "anr_ingp_field_bwd_ref16_rows_h: workspace smaller than "
-                "anr_ingp_field_bwd_ref16_rows_workspace_bytes()");
-  ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-                "anr_ingp_field_bwd_ref16_rows_h: workspace must be 256-byte aligned");
-  return field_bwd(pos, dir, ANR_F16, packed, enc, enc_stride, dirs, n_per_ray, M, nullptr,
-                   d_sigma, d_color, d_color_stride, nullptr, d_enc_stride, g_pos, g_dir, nullptr,
-                   0, stream, loss_scale, nullptr, d_enc_h, row_nz, workspace, true);
+  return field_bwd_ref16_rows("anr_ingp_field_bwd_ref16_rows_h", true, pos, dir, packed, enc,
+                              enc_stride, dirs, n_per_ray, M, d_sigma, d_color, d_color_stride,
+                              d_enc_h, d_enc_stride, g_pos, g_dir, loss_scale, row_nz, workspace,
+                              workspace_bytes, stream);
 }
 
 extern "C" int anr_ingp_field_fwd_rows(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3185,8 +3085,10 @@ extern "C" int anr_ingp_field_fwd_rows(const anr_mlp_desc* pos, const anr_mlp_de
                                        anr_stream_t stream) {
   if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_fwd_rows");
   ANR_CHECK_ARG(rows || M == 0, "anr_ingp_field_fwd_rows: null rows");
-  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, rows,
-                   sigma, color, color_stride, stream);
+  FwdForm f{};
+  f.rows = rows;
+  return field_fwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, sigma, color,
+                   color_stride, stream, f);
 }
 
 extern "C" int anr_ingp_field_bwd_rows(const anr_mlp_desc* pos, const anr_mlp_desc* dir,
@@ -3199,9 +3101,12 @@ extern "C" int anr_ingp_field_bwd_rows(const anr_mlp_desc* pos, const anr_mlp_de
                                        anr_stream_t stream) {
   if (M != 0 && multi_band(pos, dir)) return refuse_bands("anr_ingp_field_bwd_rows");
   ANR_CHECK_ARG(rows || M == 0, "anr_ingp_field_bwd_rows: null rows");
-  return field_bwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, rows,
-                   d_sigma, d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir,
-                   workspace, workspace_bytes, stream);
+  BwdForm f{};
+  f.rows = rows;
+  f.workspace = workspace;
+  f.workspace_bytes = workspace_bytes;
+  return field_bwd(pos, dir, mma_dtype, packed, enc, enc_stride, dirs, n_per_ray, M, d_sigma,
+                   d_color, d_color_stride, d_enc, d_enc_stride, g_pos, g_dir, stream, f);
 }
 
 #ifdef FIELD_STAMP

@@ -621,7 +621,7 @@ static int launch(bool bwd, const Args& a, hipStream_t st) {
   // waves, 64 flush adds per weight instead of 512) measured 0.104 ms against 0.057 ms with
   // one tile per wave: the serial tile walk costs more than the contended flush saves.
   // fwd: at most 2,048 blocks, grid-stride.
-  const int64_t blocks = bwd ? persistent_blocks(work, blocks_per_cu(fn, 64 * waves, lds))
+  const int64_t blocks = bwd ? persistent_blocks(work, resident_blocks(fn, 64 * waves, lds))
                              : (work < 2048 ? work : 2048);
   if (bwd) {
     Args b = a;

@@ -29,28 +29,31 @@
 extern "C" {
 #endif
 
-/* Added to ABI 5 without a version change (additive; every ABI 5 call behaves as it did):
- * anr_ingp_render -- the forward-only render (hash grid, field and composite in one kernel,
- * no per-sample output), in reference and build numerics;
- * multi-band extinction in the fused field -- dir descriptors of 16..18 inputs (S = 20 -
- * n_input = 2..4 density outputs), refused before, are accepted by anr_ingp_field_supported
- * / _packed_size / _pack / _fwd / _density / _bwd / _bwd_workspace_bytes, with sigma and
- * d_sigma (M, S); no signature changes (see "K6 + K7 fused" below);
- * the include_height input -- 4-D hash grids (anr_hashgrid_init_nd; forward, backward and
- * planes take its descriptors), anr_prep_params.mode 2 in anr_sample_uniform_bins ((B,N,4)
- * coords), anr_append_heights and anr_append_heights_f64.
- * ABI 5 (r06): the row-bit hash-grid backward and the f16-row field backward with its pos /
- * list-pass workspace -- anr_hashgrid_bwd_rows, anr_ingp_field_bwd_ref16_rows and
- * anr_ingp_field_bwd_ref16_rows_workspace_bytes;
- * added since without a version change (additive): anr_ingp_field_fwd_h,
- * anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16 interchange between the
- * field and the f16 composite); anr_composite_ref16_fwd_park and
- * anr_composite_ref16_bwd_parked (the forward parks T, exp and the surface product for its
- * backward, which then skips its replay of the forward); anr_grad_quantize_add_f16 (the
- * per-call f16 rounding of a tcnn module's parameter gradient, added to the caller's).
- * ABI 4 (r06): anr_ingp_hash_field_fwd. ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused
- * field entry points' enc_stride < 0
- * selecting the level-quad-plane layout it writes. */
+/* Version history, newest first.
+ * ABI 5 (r06, the current version): the row-bit hash-grid backward and the f16-row field
+ *   backward with its pos / list-pass workspace -- anr_hashgrid_bwd_rows,
+ *   anr_ingp_field_bwd_ref16_rows and anr_ingp_field_bwd_ref16_rows_workspace_bytes.
+ *   Added to ABI 5 since, without a version change (additive; every ABI 5 call behaves as it
+ *   did), oldest first:
+ *   - the include_height input -- 4-D hash grids (anr_hashgrid_init_nd; forward, backward and
+ *     planes take its descriptors), anr_prep_params.mode 2 in anr_sample_uniform_bins
+ *     ((B,N,4) coords), anr_append_heights and anr_append_heights_f64;
+ *   - anr_ingp_field_fwd_h and anr_ingp_field_bwd_ref16_rows_h (the reference numerics' f16
+ *     interchange between the field and the f16 composite); anr_composite_ref16_fwd_park and
+ *     anr_composite_ref16_bwd_parked (the forward parks T, exp and the surface product for
+ *     its backward, which then skips its replay of the forward);
+ *   - multi-band extinction in the fused field -- dir descriptors of 16..18 inputs (S = 20 -
+ *     n_input = 2..4 density outputs), refused before, are accepted by
+ *     anr_ingp_field_supported / _packed_size / _pack / _fwd / _density / _bwd /
+ *     _bwd_workspace_bytes, with sigma and d_sigma (M, S); no signature changes (see
+ *     "K6 + K7 fused" below);
+ *   - anr_grad_quantize_add_f16 (the per-call f16 rounding of a tcnn module's parameter
+ *     gradient, added to the caller's);
+ *   - anr_ingp_render -- the forward-only render (hash grid, field and composite in one
+ *     kernel, no per-sample output), in reference and build numerics.
+ * ABI 4 (r06): anr_ingp_hash_field_fwd.
+ * ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused field entry points' enc_stride < 0
+ *   selecting the level-quad-plane layout it writes. */
 #define ANR_ABI_VERSION 5
 
 enum anr_dtype { ANR_F32 = 0, ANR_F16 = 1, ANR_BF16 = 2 };

@@ -193,6 +193,41 @@ def test_multiband_field_matches_oracle(dev, S, width, nhd, R, mma):
         close(pad, pad_ref, rel=rb, atol=1e-7)
 
 
+@pytest.mark.parametrize("mma", ["f16", "bf16"])
+@pytest.mark.parametrize("S", [4, 2, 3])
+def test_multiband_bwd_without_density_gradient(dev, S, mma):
+    """No d_sigma: the backward's general d_color layout at S > 1 (the other cases here pass
+    one and run the fast layout). dL/denc and both parameter gradients against the oracle's
+    for the colour term alone, same tolerances as test_multiband_field_matches_oracle."""
+    from atmonr_amd import _lib
+
+    width, nhd, R = 64, 2, 29
+    code = _lib.BF16 if mma == "bf16" else _lib.F16
+    rb = 5e-2 if mma == "bf16" else 2e-2
+    c = _case(S, width, nhd, R, mma)
+    M, n_pp, n_pd = c["M"], c["n_pp"], c["n_pd"]
+    lib = _lib.load()
+    pdsc, ddsc = _descs(S, width, nhd)
+    pb, db = ctypes.byref(pdsc), ctypes.byref(ddsc)
+    pp_d, pd_d = c["pp"].to(dev), c["pd"].to(dev)
+    enc_d, dirs_d = c["enc_h"].to(dev), c["dirs"].to(dev)
+    packed = _pack(lib, dev, pb, db, code, pp_d, pd_d)
+    g_enc, g_p, g_d = torch.autograd.grad((c["rc"] * c["dcol"].double()).sum(),
+                                          (c["e64"], c["pr_p"], c["pr_d"]), retain_graph=True)
+    dcol_d = c["dcol"].to(dev)
+    d_enc = torch.full((M, 32), float("nan"), device=dev)
+    g_pos, g_dir = torch.zeros(n_pp, device=dev), torch.zeros(n_pd, device=dev)
+    ws_bytes = lib.anr_ingp_field_bwd_workspace_bytes(pb, db, code, M)
+    ws = torch.empty(max(1, ws_bytes // 4), device=dev)
+    _lib.call("anr_ingp_field_bwd", pb, db, code, packed.data_ptr(), enc_d.data_ptr(), 32,
+              dirs_d.data_ptr(), N_PER_RAY, M, None, dcol_d.data_ptr(), NB, d_enc.data_ptr(), 32,
+              g_pos.data_ptr(), g_dir.data_ptr(), ws.data_ptr() if ws_bytes else None, ws_bytes,
+              _lib.stream(dev))
+    close(d_enc, g_enc, rel=rb, atol=1e-7)
+    close(g_pos, g_p, rel=rb, atol=1e-7)
+    close(g_dir, g_d, rel=rb, atol=1e-7)
+
+
 def test_multiband_one_band_at_a_time(dev):
     """d_color = 0 and d_sigma nonzero in band j only: dL/denc is the oracle's for that band
     alone, and differs between bands (S = 4, W = 64, two dir hidden layers, f16)."""
@@ -262,11 +297,14 @@ def test_multiband_density_equals_field_sigma(dev, S, width, nhd, M, mma):
 
 
 @pytest.mark.parametrize("mma", ["f16", "bf16"])
-@pytest.mark.parametrize("S", [4, 2])
+@pytest.mark.parametrize("S", [4, 2, 3])
 def test_multiband_enc_quad_planes_equal_rows(dev, S, mma):
     """Row layout against level-quad planes (enc_stride = -plane) at M = 37 * 29: bit-identical
     sigma, colour, density and dL/denc; parameter gradients up to the atomic flush order.
-    The uniform-tile forward (48 samples per ray) and the general one (37) both run."""
+    The uniform-tile forward (48 samples per ray) and the general one (37) both run, and at
+    48 per ray the uniform-tile form's sigma and colour are bit-identical to the general
+    form's (anr_ingp_field_force_fwd(0); test_multiband_field_matches_oracle holds that one
+    to the oracle), as test_field_fwd_uniform_tile_matches_general asks at S = 1."""
     from atmonr_amd import _lib
 
     width, nhd = 64, 2
@@ -305,6 +343,17 @@ def test_multiband_enc_quad_planes_equal_rows(dev, S, mma):
             assert torch.isnan(sigma[M:]).all() and torch.isfinite(sigma[:M]).all()
             out[name] = (sigma[:M], color, dens, d_enc, g_pos, g_dir)
         assert torch.equal(out["rows"][0], out["rows"][2])
+        prev = lib.anr_ingp_field_force_fwd(0)
+        try:
+            sigma = torch.full((M + 4, S), float("nan"), device=dev)
+            color = torch.empty(M, NB, device=dev)
+            _lib.call("anr_ingp_field_fwd", pb, db, code, packed.data_ptr(), enc.data_ptr(), 32,
+                      dirs.data_ptr(), n_per_ray, M, sigma.data_ptr(), color.data_ptr(), NB, s)
+            torch.cuda.synchronize(dev)
+        finally:
+            lib.anr_ingp_field_force_fwd(prev)
+        assert torch.isnan(sigma[M:]).all()
+        assert torch.equal(sigma[:M], out["rows"][0]) and torch.equal(color, out["rows"][1])
         for a, b in zip(out["rows"][:4], out["planes"][:4]):
             assert torch.equal(a, b)
         for a, b in zip(out["rows"][4:], out["planes"][4:]):

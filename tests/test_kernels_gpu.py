@@ -1008,13 +1008,14 @@ def test_field_fwd_uniform_tile_matches_general(mma, n_per_ray, R, extra, width,
         assert torch.isnan(a[M:]).all() and torch.isnan(b[M:]).all()  # nothing past row M
 
 
-def _field_torch_f32(enc_h, dirs, n_per_ray, pp, pd, width, nhd, nb, h):
+def _field_torch_f32(enc_h, dirs, n_per_ray, keep, pp, pd, width, nhd, nb, h):
     """The fused field in torch f32 on the device with the kernel's 16-bit roundings (h):
-    pos 32 -> W -> 16, SH2 | pos_out[1:16] | 1.0 padding, dir 32 -> W (x nhd) -> 16 -> nb."""
+    pos 32 -> W -> 16, SH2 | pos_out[1:16] | 1.0 padding, dir 32 -> W (x nhd) -> 16 -> nb.
+    Row r of enc_h is sample keep[r] of the ray-major samples."""
     P0 = h(pp[: 32 * width]).view(width, 32)
     P1 = h(pp[32 * width:]).view(16, width)
     po = h(torch.relu(h(enc_h.float()) @ P0.T)) @ P1.T
-    d = dirs.repeat_interleave(n_per_ray, 0)[: po.shape[0]] * 2 - 1  # a ragged last ray
+    d = dirs.repeat_interleave(n_per_ray, 0)[keep] * 2 - 1  # a ragged last ray
     c1 = 0.48860251190291987
     sh = torch.stack([torch.full_like(d[:, 0], 0.28209479177387814), -c1 * d[:, 1],
                       c1 * d[:, 2], -c1 * d[:, 0]], 1)
@@ -1029,22 +1030,37 @@ def _field_torch_f32(enc_h, dirs, n_per_ray, pp, pd, width, nhd, nb, h):
     return torch.relu(po[:, 0]), torch.relu(x[:, :nb])
 
 
-def _field_vs_torch_f32(dev, mma, R, n_per_ray, extra=0):
+def _field_vs_torch_f32(dev, mma, R, n_per_ray, extra=0, nb=4, d_sigma=True, rows=False):
     """Fused field forward and backward (width 64, 2 dir layers) on R rays of n_per_ray
     samples plus `extra` rows of one more ray, against the same network in torch f32 on the
     device with the kernel's 16-bit roundings (autograd for the gradients), plus up to two
-    rays of spot rows against the f64 CPU oracle. Tolerances (of the largest value): sigma /
+    rays of spot rows against the f64 CPU oracle. ``nb`` colour outputs; ``d_sigma=False``
+    passes no density gradient (either selects the backward's general d_color layout);
+    ``rows`` goes through the _rows entries with the same number of rows thinned out of
+    half as many more samples (every third one dropped, so the list crosses a ray inside a
+    tile): outputs and incoming gradients are then indexed through the list, and the
+    samples that are not listed stay unwritten.
+    Tolerances (of the largest value): sigma /
     color 2e-2 (f16) / 4e-2 (bf16) on every row; d_enc within 5e-2 on >= 99.9 % of rows (a
     ReLU input within rounding of 0 can switch sides between two evaluation orders, changing
     that row's gradient path); parameter gradients (sums over the rows) 2e-2 / 5e-2 relative
     L2."""
     from atmonr_amd import _lib
 
-    width, nhd, nb = 64, 2, 4
+    width, nhd = 64, 2
     M = R * n_per_ray + extra
     bf = mma == "bf16"
     code = _lib.BF16 if bf else _lib.F16
     rtype = torch.bfloat16 if bf else torch.float16
+    sfx = "_rows" if rows else ""
+    keep = torch.arange(M, device=dev)  # sample of row r
+    if rows:
+        keep += keep // 2
+    D = int(keep[-1]) + 1  # samples
+    # bound to a name for the whole function: a temporary's block would be handed to the next
+    # allocation, and the kernels would read that tensor's values as row indices
+    row_list = keep.int() if rows else None
+    kept = (row_list.data_ptr(),) if rows else ()
     h = lambda t: t.to(rtype).float()
     rf, rg = (4e-2, 5e-2) if bf else (2e-2, 2e-2)
     g = torch.Generator(device=dev).manual_seed(11)
@@ -1054,46 +1070,53 @@ def _field_vs_torch_f32(dev, mma, R, n_per_ray, extra=0):
     pp = torch.randn(lib.anr_mlp_n_params(pb), device=dev, generator=g) * (2.0 / 32) ** 0.5
     pd = torch.randn(lib.anr_mlp_n_params(db), device=dev, generator=g) * (2.0 / width) ** 0.5
     enc = (torch.rand(M, 32, device=dev, generator=g) * 2 - 1).half()
-    n_rays = R + (1 if extra else 0)
+    n_rays = -(-D // n_per_ray)
     dirs = torch.nn.functional.normalize(torch.randn(n_rays, 3, device=dev, generator=g), dim=1) * 0.5 + 0.5
     s = _lib.stream(dev)
     packed = torch.empty(lib.anr_ingp_field_packed_size(pb, db), device=dev, dtype=torch.float16)
     _lib.call("anr_ingp_field_pack", pb, db, code, pp.data_ptr(), pd.data_ptr(),
               packed.data_ptr(), s)
-    sigma, color = torch.empty(M, device=dev), torch.empty(M, nb, device=dev)
-    _lib.call("anr_ingp_field_fwd", pb, db, code, packed.data_ptr(), enc.data_ptr(), 32,
-              dirs.data_ptr(), n_per_ray, M, sigma.data_ptr(), color.data_ptr(), nb, s)
-    dcol = torch.randn(M, nb, device=dev, generator=g) * 1e-3
-    dsig = torch.randn(M, device=dev, generator=g) * 1e-3
+    sigma = torch.full((D,), float("nan"), device=dev)
+    color = torch.full((D, nb), float("nan"), device=dev)
+    _lib.call("anr_ingp_field_fwd" + sfx, pb, db, code, packed.data_ptr(), enc.data_ptr(), 32,
+              dirs.data_ptr(), n_per_ray, M, *kept, sigma.data_ptr(), color.data_ptr(), nb, s)
+    dcol = torch.randn(D, nb, device=dev, generator=g) * 1e-3
+    dsig = torch.randn(D, device=dev, generator=g) * 1e-3
     d_enc = torch.empty(M, 32, device=dev)
     g_pos, g_dir = torch.zeros_like(pp), torch.zeros_like(pd)
     ws_bytes = lib.anr_ingp_field_bwd_workspace_bytes(pb, db, code, M)
     ws = torch.empty(max(1, ws_bytes // 4), device=dev)
-    _lib.call("anr_ingp_field_bwd", pb, db, code, packed.data_ptr(), enc.data_ptr(), 32,
-              dirs.data_ptr(), n_per_ray, M, dsig.data_ptr(), dcol.data_ptr(), nb,
-              d_enc.data_ptr(), 32, g_pos.data_ptr(), g_dir.data_ptr(), ws.data_ptr(),
-              ws_bytes, s)
+    _lib.call("anr_ingp_field_bwd" + sfx, pb, db, code, packed.data_ptr(), enc.data_ptr(), 32,
+              dirs.data_ptr(), n_per_ray, M, *kept, dsig.data_ptr() if d_sigma else None,
+              dcol.data_ptr(), nb, d_enc.data_ptr(), 32, g_pos.data_ptr(), g_dir.data_ptr(),
+              ws.data_ptr(), ws_bytes, s)
     # torch f32 reference with autograd
     e = enc.float().requires_grad_(True)
     tp, td = pp.clone().requires_grad_(True), pd.clone().requires_grad_(True)
-    rs, rc = _field_torch_f32(e, dirs, n_per_ray, tp, td, width, nhd, nb, h)
-    ((rc * dcol).sum() + (rs * dsig).sum()).backward()
-    close(sigma, rs.detach(), rel=rf, atol=1e-5)
-    close(color, rc.detach(), rel=rf, atol=1e-5)
+    rs, rc = _field_torch_f32(e, dirs, n_per_ray, keep, tp, td, width, nhd, nb, h)
+    ((rc * dcol[keep]).sum() + ((rs * dsig[keep]).sum() if d_sigma else 0.0)).backward()
+    close(sigma[keep], rs.detach(), rel=rf, atol=1e-5)
+    close(color[keep], rc.detach(), rel=rf, atol=1e-5)
+    listed = torch.zeros(D, dtype=torch.bool, device=dev)
+    listed[keep] = True
+    assert torch.isnan(sigma[~listed]).all() and torch.isnan(color[~listed]).all()
     row_err = (d_enc - e.grad).abs().amax(1)
     ok = (row_err <= 5e-2 * e.grad.abs().max()).float().mean().item()
     assert ok >= 0.999, ok
     for a, b in ((g_pos, tp.grad), (g_dir, td.grad)):
         assert ((a - b).norm() / b.norm()).item() <= rg
-    # spot rows against the f64 CPU oracle (two whole rays, so n_per_ray stays intact)
+    # spot rows against the f64 CPU oracle: the rows of two whole rays, ray by ray (R >= 1
+    # and extra < n_per_ray: rays 0..R-1 are whole, the ragged one is never drawn)
     rays = torch.randperm(R, generator=torch.Generator().manual_seed(3))[:2]
-    rows = (rays[:, None] * n_per_ray + torch.arange(n_per_ray)[None]).reshape(-1).to(dev)
+    ray_of = (keep // n_per_ray).cpu()
+    spot = torch.cat([(ray_of == r).nonzero().flatten() for r in rays.tolist()]).to(dev)
+    per_ray = torch.stack([(ray_of == r).sum() for r in rays.tolist()])
     half = "bf16" if bf else True
-    rs64, rc64, _, _ = _field_ref(enc[rows].cpu().double(), dirs[rays.to(dev)].cpu().double(),
-                                  n_per_ray, pp.cpu().double(), pd.cpu().double(), width, nhd,
+    rs64, rc64, _, _ = _field_ref(enc[spot].cpu().double(), dirs[rays.to(dev)].cpu().double(),
+                                  per_ray, pp.cpu().double(), pd.cpu().double(), width, nhd,
                                   nb, half)
-    close(sigma[rows], rs64, rel=rf, atol=1e-5)
-    close(color[rows], rc64, rel=rf, atol=1e-5)
+    close(sigma[keep[spot]], rs64, rel=rf, atol=1e-5)
+    close(color[keep[spot]], rc64, rel=rf, atol=1e-5)
 
 
 @pytest.mark.timeout(300)
@@ -1114,6 +1137,20 @@ def test_ingp_field_grid_clamps(dev, mma, R, n_per_ray, extra):
     largest possible grid (every wavefront walks more than one tile), and the last tile is
     ragged."""
     _field_vs_torch_f32(dev, mma, R, n_per_ray, extra)
+
+
+@pytest.mark.parametrize("mma", ["f16", "bf16"])
+@pytest.mark.parametrize("rows", [False, True])
+@pytest.mark.parametrize("nb,d_sigma", [(3, True), (4, False), (4, True)])
+@pytest.mark.parametrize("n_per_ray", [40, 33])
+def test_ingp_field_general_forms(dev, mma, rows, nb, d_sigma, n_per_ray):
+    """The launch forms the larger cases leave out, same oracle and tolerances: the
+    backward's general d_color layout (3 colour outputs, or no density gradient) in build
+    numerics, dense and through the _rows entries (whose forward this also is at kernel
+    level; with 4 outputs and a density gradient, the fast layout with rows). One ray of 40
+    samples: the general forward (40 % 16 != 0), ragged 16- and 32-row tiles; of 33: one
+    row in the last tile of each, on the smallest grid."""
+    _field_vs_torch_f32(dev, mma, 1, n_per_ray, nb=nb, d_sigma=d_sigma, rows=rows)
 
 
 @pytest.mark.parametrize("tdt", ["f16", "f32"])

@@ -18,7 +18,7 @@ from oracle import ref_f16
 pytestmark = pytest.mark.gpu
 
 
-def _field(dev, width, nhd, nb, M, R, seed, dir_gain=1.0):
+def _field(dev, width, nhd, nb, M, R, seed, dir_gain=1.0, mma=None):
     """Descriptors, packed weights (the dir network's scaled by dir_gain per layer), f16
     encodings and directions of a field of the pipelines' shapes."""
     from atmonr_amd import _lib
@@ -33,8 +33,8 @@ def _field(dev, width, nhd, nb, M, R, seed, dir_gain=1.0):
     enc = (torch.rand(M, 32, device=dev, generator=g) * 2 - 1).half()
     dirs = torch.rand(R, 3, device=dev, generator=g)
     packed = torch.empty(lib.anr_ingp_field_packed_size(pb, db), device=dev, dtype=torch.float16)
-    _lib.call("anr_ingp_field_pack", pb, db, _lib.F16, pp.data_ptr(), pd.data_ptr(),
-              packed.data_ptr(), _lib.stream(dev))
+    _lib.call("anr_ingp_field_pack", pb, db, _lib.F16 if mma is None else mma, pp.data_ptr(),
+              pd.data_ptr(), packed.data_ptr(), _lib.stream(dev))
     return {"keep": (pdsc, ddsc), "pb": pb, "db": db, "pp": pp, "pd": pd, "enc": enc,
             "dirs": dirs, "packed": packed, "g": g}
 
@@ -70,6 +70,29 @@ def test_field_fwd_h_is_half_of_f32_outputs(dev, width, nhd, n_per_ray, R, M):
     # both kinds of value occur: a negative pre-activation (stored 0) and an overflow
     assert (col16[:M] == 0).any() and (sig16[:M] == 0).any()
     assert torch.isinf(col16[:M]).any() and (col32[:M] > 65504).any()
+
+
+@pytest.mark.parametrize("n_per_ray,R,M", [(64, 3, 192), (48, 5, 233)])
+def test_field_fwd_h_bf16_is_half_of_f32_outputs(dev, n_per_ray, R, M):
+    """The same equality with bf16 MFMA (the pipelines run f16 outputs in reference numerics,
+    which are f16; the entry takes both), in the uniform-tile and the general form."""
+    from atmonr_amd import _lib
+
+    f = _field(dev, 64, 2, 4, M, R, seed=22, mma=_lib.BF16)
+    s = _lib.stream(dev)
+    sig32 = torch.full((M + 16,), float("nan"), device=dev)
+    col32 = torch.full((M + 16, 4), float("nan"), device=dev)
+    sig16, col16 = sig32.half(), col32.half()
+    for name, sig, col in (("anr_ingp_field_fwd", sig32, col32),
+                           ("anr_ingp_field_fwd_h", sig16, col16)):
+        _lib.call(name, f["pb"], f["db"], _lib.BF16, f["packed"].data_ptr(), f["enc"].data_ptr(),
+                  32, f["dirs"].data_ptr(), n_per_ray, M, sig.data_ptr(), col.data_ptr(), 4, s)
+    torch.cuda.synchronize(dev)
+    assert torch.isfinite(sig32[:M]).all() and torch.isfinite(col32[:M]).all()
+    assert (col32[:M] > 0).any() and (sig32[:M] > 0).any()
+    assert torch.equal(sig16[:M], sig32[:M].half())
+    assert torch.equal(col16[:M], col32[:M].half())
+    assert torch.isnan(sig16[M:]).all() and torch.isnan(col16[M:]).all()
 
 
 # ------------------------------------------------------------------ 2. field backward

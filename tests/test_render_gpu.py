@@ -95,6 +95,27 @@ def test_reference_numerics_bit_for_bit(scene, dev, B, N, width, dir_layers):
     _same_bits(p.render(batch, u=u), ren, "second call, explicit draws")
 
 
+def test_reference_numerics_with_bf16_mfma(scene, dev, monkeypatch):
+    """anr_ingp_render takes reference numerics with bf16 MFMA, a pair no pipeline asks for
+    (reference numerics are tcnn's f16). It keeps the contract of the f16 case: its maps are
+    the bits of the two-kernel forward (hash planes, anr_ingp_field_fwd_h, the f16 composite)
+    run on the same bf16 weights. (40, 128): one carry, as above. The f16 render of the same
+    rays differs, so the bf16 kernels did run."""
+    from atmonr_amd import _lib, field
+
+    B, N = 40, 128
+    p = _pipe(scene, dev, _config(N), numerics="reference")
+    assert p.render_kernel_refusal() is None
+    batch, u = _batch(scene, dev, B, N)
+    with monkeypatch.context() as m:
+        m.setattr(field, "_mma_code", lambda pipe: _lib.BF16)
+        _, fwd = rc.make_alive(p, batch, u)
+        ren = p.render(batch, u=u, fused=True)
+    _same_bits(ren, fwd, "bf16 MFMA")
+    ren_f16 = p.render(batch, u=u, fused=True)
+    assert any(not torch.equal(ren_f16[k], ren[k]) for k in rc.MAPS)
+
+
 # ------------------------------------------------------------------ 2. an f16 alpha of 1
 def test_alpha_of_exactly_one(scene, dev):
     """Scaled until some sample has sigma * delta > 9 (exp rounds to 0 in f16, alpha to 1, q2

@@ -290,6 +290,17 @@ _SIGNATURES = {
         c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, c_float, _P, _P]),
     "anr_occupancy_compact": (
         c_int32, [_P, c_int64, _P, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P]),
+    "anr_voxel_n_blocks": (c_int64, [c_int64]),
+    "anr_voxel_traverse": (
+        c_int32,
+        [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P,
+         c_int32, _P],
+    ),
+    "anr_voxel_count": (c_int32, [_P, c_int32, c_int32, c_int32, c_int64, _P, _P]),
+    "anr_voxel_compact": (
+        c_int32,
+        [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, _P, c_int64, _P, _P],
+    ),
     "anr_composite_force_generic": (c_int32, [c_int32]),
     "anr_composite_fwd": (
         c_int32,

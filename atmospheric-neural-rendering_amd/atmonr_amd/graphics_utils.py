@@ -5,6 +5,10 @@ color_surf)`` return exactly the reference's tuples. Both are differentiable w.r
 color, sigma, color_surf and z_vals (the NeRF fine pass back-propagates into z through
 sample_pdf). Arithmetic is f32 inside the kernel for any storage dtype; the outputs
 have ``color.dtype`` as in the reference (graphics_utils.py:28).
+
+``voxel_traversal(u, end)`` (graphics_utils.py:80-147) returns the voxels a set of segments
+passes through: an exact f64 walk into a bitmap (csrc/voxels.hip) and the bitmap's ordered
+compaction. :class:`VoxelBitmap` is the bitmap itself, for callers that feed it chunks of rays.
 """
 
 from __future__ import annotations
@@ -217,3 +221,106 @@ def render_with_surface(z_vals, color, sigma, color_surf, z_scale: float = 1.0):
     """graphics_utils.py:52-77. Returns (color_map, alpha, weights, atmo, surf)."""
     _check(z_vals, color, sigma)
     return _CompositeFn.apply(z_vals, color, sigma, color_surf, z_scale, True)
+
+
+DEFAULT_MAX_BITMAP_BYTES = 4 << 30
+
+
+class VoxelBitmap:
+    """One bit per voxel of the box ``lo <= (i, j, k) <= hi`` (inclusive int corners), i
+    fastest, rows padded to whole uint32 words (include/anr.h, "Global-grid extract").
+    :meth:`add` ORs the voxels of a chunk of rays into it; :meth:`voxels` compacts it."""
+
+    def __init__(self, lo, hi, device, max_bitmap_bytes: int = DEFAULT_MAX_BITMAP_BYTES):
+        self.lo = tuple(int(v) for v in lo)
+        self.ext = tuple(int(h) - int(l) + 1 for l, h in zip(lo, hi))
+        if min(self.ext) < 1:
+            raise ValueError(f"voxel box {self.lo} .. {tuple(hi)} is empty")
+        self.row_pitch = (self.ext[0] + 31) // 32 * 32
+        self.n_words = self.row_pitch // 32 * self.ext[1] * self.ext[2]
+        if self.n_words * 4 > max_bitmap_bytes:
+            raise ValueError(
+                f"voxel box of {self.ext[0]} x {self.ext[1]} x {self.ext[2]} voxels from "
+                f"{self.lo} needs a bitmap of {self.n_words * 4} bytes, above the limit of "
+                f"{max_bitmap_bytes} bytes (max_bitmap_bytes)")
+        self.device = torch.device(device)
+        # int32 storage (torch has no uint32 arithmetic); the kernels see uint32 words
+        self.words = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def bounds(u: torch.Tensor, end: torch.Tensor):
+        """Inclusive int corners of the floored endpoints of the rays whose two endpoints are
+        finite (``amin`` / ``amax``, a few million rays at a time), or None without any."""
+        lo = hi = None
+        for s in range(0, u.shape[0], 1 << 22):
+            pts = torch.stack([u[s:s + (1 << 22)], end[s:s + (1 << 22)]], dim=1).double()
+            pts = torch.floor(pts[torch.isfinite(pts).all(dim=2).all(dim=1)]).reshape(-1, 3)
+            if pts.shape[0] == 0:
+                continue
+            clo, chi = pts.amin(dim=0), pts.amax(dim=0)
+            lo = clo if lo is None else torch.minimum(lo, clo)
+            hi = chi if hi is None else torch.maximum(hi, chi)
+        if lo is None:
+            return None
+        lo, hi = lo.tolist(), hi.tolist()
+        if max(abs(v) for v in lo + hi) >= 2.0 ** 31 - 1:
+            raise ValueError(f"voxel coordinates {lo} .. {hi} do not fit int32")
+        return [int(v) for v in lo], [int(v) for v in hi]
+
+    def add(self, u: torch.Tensor, end: torch.Tensor, shortcut: bool = True) -> None:
+        if u.shape != end.shape or u.dim() != 2 or u.shape[1] != 3:
+            raise ANRError("voxel traversal: u and end must both be (R, 3)")
+        u = u.to(device=self.device, dtype=torch.float64).contiguous()
+        end = end.to(device=self.device, dtype=torch.float64).contiguous()
+        call("anr_voxel_traverse", ptr(u), ptr(end), u.shape[0], *self.lo, *self.ext,
+             self.row_pitch, ptr(self.words), ptr(self.counters), int(bool(shortcut)),
+             _lib.stream(self.device))
+
+    def skipped_rays(self) -> int:
+        """Rays that marked nothing because an endpoint was not finite."""
+        return int(self.counters[0].item())
+
+    def voxels(self) -> torch.Tensor:
+        """(n, 3) int32 (i, j, k) of the set bits in ascending bitmap order (k slowest, i
+        fastest). Raises when a ray had a voxel outside the box."""
+        outside = int(self.counters[1].item())
+        if outside:
+            raise ANRError(f"voxel traversal: {outside} voxels of rays that leave the box "
+                           f"{self.lo} + {self.ext} were not marked")
+        st = _lib.stream(self.device)
+        n_blocks = _lib.load().anr_voxel_n_blocks(self.n_words)
+        counts = torch.empty(n_blocks, dtype=torch.int32, device=self.device)
+        call("anr_voxel_count", ptr(self.words), *self.ext, self.row_pitch, ptr(counts), st)
+        ends = torch.cumsum(counts, dim=0, dtype=torch.int64)
+        offsets = (ends - counts).contiguous()
+        n = int(ends[-1].item())
+        out = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+        call("anr_voxel_compact", ptr(self.words), *self.lo, *self.ext, self.row_pitch,
+             ptr(offsets), n, ptr(out), st)
+        return out
+
+
+def voxel_traversal(u: torch.Tensor, end: torch.Tensor, unique_only: bool = True,
+                    max_bitmap_bytes: int = DEFAULT_MAX_BITMAP_BYTES) -> torch.Tensor:
+    """graphics_utils.py:80-147: all voxels (edge 1) that the segments ``u -> end`` pass
+    through. ``u``, ``end``: GPU tensors (R, 3) of any float dtype, widened to f64. Returns
+    the unique voxels as (n, 3) int32, sorted with k slowest and i fastest -- the same for any
+    order or chunking of the rays and from run to run.
+
+    The walk is exact in f64 (csrc/voxels.hip): the reference accumulates its crossing times
+    in the input's precision and can leave the true path at large coordinates; its indices
+    are int16, these int32. ``unique_only=False`` returns the same tensor: the voxels are
+    collected in a bitmap, which has no duplicates. Rays with a non-finite endpoint are
+    skipped. The bitmap spans the bounding box of the floored endpoints; a box that needs
+    more than ``max_bitmap_bytes`` raises ValueError (the box is not tiled)."""
+    if not (u.is_cuda and end.is_cuda):
+        raise ANRError("voxel_traversal needs GPU tensors (got a CPU tensor)")
+    if u.shape != end.shape or u.dim() != 2 or u.shape[1] != 3:
+        raise ANRError("voxel_traversal: u and end must both be (R, 3)")
+    box = VoxelBitmap.bounds(u, end)
+    if box is None:
+        return torch.empty((0, 3), dtype=torch.int32, device=u.device)
+    bitmap = VoxelBitmap(box[0], box[1], u.device, max_bitmap_bytes)
+    bitmap.add(u, end)
+    return bitmap.voxels()

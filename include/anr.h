@@ -50,7 +50,9 @@ extern "C" {
  *   - anr_grad_quantize_add_f16 (the per-call f16 rounding of a tcnn module's parameter
  *     gradient, added to the caller's);
  *   - anr_ingp_render -- the forward-only render (hash grid, field and composite in one
- *     kernel, no per-sample output), in reference and build numerics.
+ *     kernel, no per-sample output), in reference and build numerics;
+ *   - anr_voxel_traverse, anr_voxel_n_blocks, anr_voxel_count and anr_voxel_compact (the
+ *     global-grid extract's exact voxel traversal into a bitmap and its ordered compaction).
  * ABI 4 (r06): anr_ingp_hash_field_fwd.
  * ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused field entry points' enc_stride < 0
  *   selecting the level-quad-plane layout it writes. */
@@ -507,6 +509,39 @@ int anr_occupancy_count(const float* coords, int64_t M, const uint8_t* occ, int3
 int anr_occupancy_compact(const float* coords, int64_t M, const uint8_t* occ, int32_t gx,
                           int32_t gy, int32_t gz, float zmul, const int64_t* offsets,
                           int32_t* rows, float* coords_out, anr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Global-grid extract: exact voxel traversal of rays into a bitmap, and the bitmap's ordered
+ * compaction (csrc/voxels.hip; the reference's graphics_utils.voxel_traversal and the
+ * torch.unique calls of datasets/harp2_extract.py:845-867).
+ * Box: origin (i0, j0, k0), extents (ni, nj, nk) >= 1, origin + extent <= 2^31. Bitmap: one
+ * bit per voxel, i along x and fastest, k slowest; an x-row takes row_pitch bits, a multiple
+ * of 32 that is >= ni, so bit b of word w of row (j, k) is voxel (i0 + 32 w + b, j, k); the
+ * whole bitmap is row_pitch * nj * nk bits (fewer than 2^46) of caller-zeroed uint32 words.
+ * anr_voxel_traverse: u, end (R, 3) f64, ray start and end in continuous voxel coordinates
+ * (voxel edge 1). ORs the voxels of every ray into the bitmap, so several calls accumulate.
+ * One thread per ray walks exactly sum_a |floor(end_a) - floor(u_a)| steps from floor(u);
+ * each step advances the axis (among those not at their end index, ties to the lowest) with
+ * the smallest crossing time t_a = (b_a - u_a) * (1 / d_a), b_a the next integer boundary:
+ * no accumulated time. counters: two int64, added to (the caller zeroes them): [0] rays
+ * skipped because an endpoint is not finite; [1] voxels not marked because their ray has an
+ * end voxel outside the box (such a ray marks nothing; every other ray stays inside the
+ * box). shortcut 1: a plain load skips the atomic OR of a word whose pending bits are all
+ * set already; 0: always the atomic (same result; for timing). R = 0: ANR_OK, no launch.
+ * anr_voxel_count writes counts[anr_voxel_n_blocks(row_pitch * nj * nk / 32)] (int32, set
+ * bits per block of 1024 words); the caller forms offsets = exclusive scan (int64) and the
+ * total n; anr_voxel_compact writes voxels (n_out, 3) int32 (i, j, k) in ascending bitmap
+ * order (rows past n_out are not written). ------------------------------------------- */
+int64_t anr_voxel_n_blocks(int64_t n_words);
+int anr_voxel_traverse(const double* u, const double* end, int64_t R, int32_t i0, int32_t j0,
+                       int32_t k0, int32_t ni, int32_t nj, int32_t nk, int64_t row_pitch,
+                       uint32_t* bitmap, int64_t* counters, int32_t shortcut,
+                       anr_stream_t stream);
+int anr_voxel_count(const uint32_t* bitmap, int32_t ni, int32_t nj, int32_t nk,
+                    int64_t row_pitch, int32_t* counts, anr_stream_t stream);
+int anr_voxel_compact(const uint32_t* bitmap, int32_t i0, int32_t j0, int32_t k0, int32_t ni,
+                      int32_t nj, int32_t nk, int64_t row_pitch, const int64_t* offsets,
+                      int64_t n_out, int32_t* voxels, anr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * NeRF path (configs/nerf.json): positional encoding (encoders.py:4-28) and the

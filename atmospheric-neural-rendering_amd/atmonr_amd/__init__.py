@@ -10,6 +10,7 @@ Drop-in modules mirroring the reference package ``atmonr``:
 * ``atmonr_amd.pipelines``       — Pipeline, InstantNGPPipeline, get_pipeline
 * ``atmonr_amd.optim``           — FusedAdam (AdamW / Adam)
 * ``atmonr_amd.render``          — render_rays / render_images (forward-only rendering)
+* ``atmonr_amd.video``           — orbit video of an extracted volume (scripts/make_video.py)
 * ``atmonr_amd.batch_loader``    — device-side, rank-sharded BatchLoader
 * ``atmonr_amd.datasets``        — HARP2-shaped synthetic scene
 

@@ -123,6 +123,21 @@ class GatherCol(Structure):
 
 GATHER_MAX_COLS = 8
 
+
+class Camera(Structure):
+    """anr_camera (include/anr.h): 12 floats, the row of a (F, 12) f32 camera tensor."""
+
+    _fields_ = [("eye", c_float * 3), ("forward", c_float * 3), ("right", c_float * 3),
+                ("up", c_float * 3)]
+
+
+class VolumeParams(Structure):
+    """anr_volume_params (include/anr.h)."""
+
+    _fields_ = [("absorb", c_float * 3), ("scatter", c_float * 3), ("light_dir", c_float * 3),
+                ("light_color", c_float * 3), ("primary_step", c_float),
+                ("shadow_step", c_float), ("light_gain", c_float), ("cutoff", c_float)]
+
 _SIGNATURES = {
     "anr_abi_version": (c_int32, []),
     "anr_last_error": (ctypes.c_char_p, []),
@@ -300,6 +315,11 @@ _SIGNATURES = {
     "anr_voxel_compact": (
         c_int32,
         [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, _P, c_int64, _P, _P],
+    ),
+    "anr_volume_render": (
+        c_int32,
+        [_P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(VolumeParams), _P,
+         _P],
     ),
     "anr_composite_force_generic": (c_int32, [c_int32]),
     "anr_composite_fwd": (

@@ -52,7 +52,9 @@ extern "C" {
  *   - anr_ingp_render -- the forward-only render (hash grid, field and composite in one
  *     kernel, no per-sample output), in reference and build numerics;
  *   - anr_voxel_traverse, anr_voxel_n_blocks, anr_voxel_count and anr_voxel_compact (the
- *     global-grid extract's exact voxel traversal into a bitmap and its ordered compaction).
+ *     global-grid extract's exact voxel traversal into a bitmap and its ordered compaction);
+ *   - anr_volume_render (the orbit video's single-scattering ray marcher over a dense
+ *     density cube, with anr_camera and anr_volume_params).
  * ABI 4 (r06): anr_ingp_hash_field_fwd.
  * ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused field entry points' enc_stride < 0
  *   selecting the level-quad-plane layout it writes. */
@@ -542,6 +544,54 @@ int anr_voxel_count(const uint32_t* bitmap, int32_t ni, int32_t nj, int32_t nk,
 int anr_voxel_compact(const uint32_t* bitmap, int32_t i0, int32_t j0, int32_t k0, int32_t ni,
                       int32_t nj, int32_t nk, int64_t row_pitch, const int64_t* offsets,
                       int64_t n_out, int32_t* voxels, anr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Orbit video of an extracted volume: single-scattering ray marcher over a dense density
+ * cube (csrc/volume_render.hip; the reference's scripts/make_video.py:174-194 runs OpenVDB's
+ * vdb_render, a CPU ray marcher, once per frame). The arithmetic below is this project's
+ * definition, written after vdb_render's VolumeRender and its defaults; parity with
+ * vdb_render: unpinned (neither its source nor its binary was available to compare with).
+ * density: (nx, ny, nz) f32, contiguous, z fastest, read in place (no padded or re-laid-out
+ * copy); nx * ny * nz * 4 < 2^31. Voxel (i, j, k) sits at position (i, j, k); D(p) is the
+ * trilinear interpolation of the eight voxels around floor(p) (z pairs, then y, then x, each
+ * a + w (b - a)), voxels outside the array being 0.
+ * cameras: F anr_camera in DEVICE memory. forward, right, up: an orthogonal basis, right
+ * scaled by tan(hfov / 2) and up by tan(hfov / 2) * H / W. Pixel (col, row), row 0 at the
+ * top, looks along normalize(forward + (2 (col + 1/2) / W - 1) right - (2 (row + 1/2) / H - 1)
+ * up).
+ * params: a HOST struct, read during the call. Per channel ext = -(absorb + scatter), albedo =
+ * light_color * scatter / (absorb + scatter) (0 where the denominator is 0); light_dir is a
+ * unit vector towards the light.
+ * Per pixel: the ray is clipped by a slab test to the box [-1, n_d] per axis, outside of which
+ * D is 0, giving [t0, t1] with t0 clamped to >= 0; a direction component of exactly 0
+ * constrains nothing if the eye lies inside that slab, and the ray misses otherwise. A miss
+ * writes RGBA = 0. Else, with T = (1, 1, 1) and L = (0, 0, 0), for t = primary_step *
+ * ceil(t0 / primary_step) + n * primary_step, n = 0, 1, ..., while t <= t1:
+ *   d = D(eye + t dir); if d < cutoff the step is skipped; dT = exp(ext * d * primary_step);
+ *   the shadow ray from that point along light_dir is clipped to the same box, giving [0, s1];
+ *   with sT = (1, 1, 1), for s = shadow_step, 2 shadow_step, ... <= s1: ds = D(p + s
+ *   light_dir); if ds < cutoff continue; sT *= exp(ext * ds * shadow_step / (1 + s *
+ *   light_gain)); the shadow ray stops once |sT|^2 < cutoff;
+ *   L += albedo * sT * T * (1 - dT), T *= dT; the pixel stops once |T|^2 < cutoff.
+ * rgba: (F, H, W, 4) f32 WRITTEN: RGB = L, A = 1 - (T.r + T.g + T.b) / 3.
+ * All of it in f32, in the order written, without FMA contraction (tests/volume_checks.py
+ * restates it in numpy). Frames are independent: F cameras in one launch give the bits of F
+ * launches. ANR_E_INVALID, before any launch: a null pointer, an extent < 1, a cube of 2^31
+ * bytes or more, a step that is not positive, a negative coefficient, a light_dir whose
+ * length is not 1 within 1e-3. F * H * W = 0: ANR_OK without a launch. Allocates nothing and
+ * does not synchronise. ------------------------------------------------------------------ */
+typedef struct {
+  float eye[3], forward[3], right[3], up[3];
+} anr_camera;
+typedef struct {
+  float absorb[3], scatter[3];
+  float light_dir[3], light_color[3];
+  float primary_step, shadow_step; /* in voxels */
+  float light_gain, cutoff;
+} anr_volume_params;
+int anr_volume_render(const float* density, int64_t nx, int64_t ny, int64_t nz,
+                      const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
+                      const anr_volume_params* params, float* rgba, anr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * NeRF path (configs/nerf.json): positional encoding (encoders.py:4-28) and the

@@ -11,7 +11,8 @@ Drop-in modules mirroring the reference package ``atmonr``:
 * ``atmonr_amd.optim``           — FusedAdam (AdamW / Adam)
 * ``atmonr_amd.render``          — render_rays / render_images (forward-only rendering)
 * ``atmonr_amd.video``           — orbit video of an extracted volume (scripts/make_video.py)
-* ``atmonr_amd.batch_loader``    — device-side, rank-sharded BatchLoader
+* ``atmonr_amd.sparse_volume``   — sparse volume and orbit video of a global-grid extract
+* ``atmonr_amd.batch_loader``   — device-side, rank-sharded BatchLoader
 * ``atmonr_amd.datasets``        — HARP2-shaped synthetic scene
 
 All compute goes through libanr_hip.so (include/anr.h); there is no CPU fallback.

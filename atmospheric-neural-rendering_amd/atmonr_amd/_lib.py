@@ -138,6 +138,14 @@ class VolumeParams(Structure):
                 ("light_color", c_float * 3), ("primary_step", c_float),
                 ("shadow_step", c_float), ("light_gain", c_float), ("cutoff", c_float)]
 
+
+class SparseVolumeDesc(Structure):
+    """anr_sparse_volume (include/anr.h)."""
+
+    _fields_ = [("cells", _P), ("values", _P), ("coarse", _P), ("ni", c_int32), ("nj", c_int32),
+                ("nk", c_int32), ("reserved", c_int32), ("row_pitch", c_int64),
+                ("n_values", c_int64)]
+
 _SIGNATURES = {
     "anr_abi_version": (c_int32, []),
     "anr_last_error": (ctypes.c_char_p, []),
@@ -320,6 +328,24 @@ _SIGNATURES = {
         c_int32,
         [_P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(VolumeParams), _P,
          _P],
+    ),
+    "anr_sparse_volume_coarse_words": (c_int64, [c_int32, c_int32, c_int32]),
+    "anr_sparse_volume_mark": (
+        c_int32,
+        [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P, _P],
+    ),
+    "anr_sparse_volume_popcount": (c_int32, [_P, c_int64, _P, _P]),
+    "anr_sparse_volume_place": (
+        c_int32,
+        [_P, _P, c_int64, ctypes.c_double, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+         c_int64, _P, c_int64, _P, _P],
+    ),
+    "anr_sparse_volume_sample": (
+        c_int32, [POINTER(SparseVolumeDesc), c_int32, _P, c_int64, _P, _P]),
+    "anr_sparse_volume_render": (
+        c_int32,
+        [POINTER(SparseVolumeDesc), c_int32, _P, c_int64, c_int64, c_int64, POINTER(VolumeParams),
+         _P, _P, _P],
     ),
     "anr_composite_force_generic": (c_int32, [c_int32]),
     "anr_composite_fwd": (

@@ -204,6 +204,21 @@ class GlobalGridExtractDataset:
 
     __getitem__ = __getbatch__
 
+    def volume(self, sigma: torch.Tensor, band: int = 2):
+        """The :class:`~atmonr_amd.sparse_volume.SparseVolume` of this grid's voxels with band
+        ``band`` of ``sigma`` (n, bands), as ``extract_volume`` returns it: what
+        ``make_global_video`` renders. The extinction (1/m) is multiplied by the voxel edge in
+        metres, ``grid_res / scale``, so the density is optical depth per voxel edge."""
+        from ._lib import ANRError
+        from .sparse_volume import SparseVolume
+
+        if sigma.dim() != 2 or sigma.shape[0] != len(self):
+            raise ANRError(f"sigma must be ({len(self)}, bands), got {tuple(sigma.shape)}")
+        if not -sigma.shape[1] <= band < sigma.shape[1]:
+            raise ANRError(f"band {band} of a sigma with {sigma.shape[1]} bands")
+        return SparseVolume.from_voxels(self.voxels, sigma[:, band].to(self.device),
+                                        self.grid_res / self.scale)
+
     def dump(self, path: Path | str, sigma: torch.Tensor) -> None:
         """The reference's output without the OpenVDB bindings (harp2_extract.py:919-934):
         ``voxels.npy`` and ``sigma.npy`` beside ``path`` (the reference writes them into the

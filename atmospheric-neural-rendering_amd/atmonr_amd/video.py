@@ -183,6 +183,30 @@ def read_ppm(path) -> np.ndarray:
     return np.frombuffer(parts[3], dtype=np.uint8, count=w * h * 3).reshape(h, w, 3)
 
 
+def stitch_frames(result: dict, out_dir, video_path, frame_rate: int, width: int,
+                  height: int) -> dict:
+    """The script's ffmpeg call over ``out_dir``'s ``%06d.ppm`` frames, if a ``video_path`` is
+    given and an ``ffmpeg`` binary is already on PATH; fills ``result["video"]`` and
+    ``result["ffmpeg"]`` (what happened) and returns ``result``."""
+    out_dir = Path(out_dir)
+    ffmpeg = shutil.which("ffmpeg")
+    if video_path is None:
+        result["ffmpeg"] = "not asked for (no video_path); the frames stay"
+    elif ffmpeg is None:
+        result["ffmpeg"] = "no ffmpeg binary on PATH; the frames stay"
+    else:
+        cmd = [ffmpeg, "-framerate", str(frame_rate), "-i", str(out_dir / "%06d.ppm"), "-c:v",
+               "libx264", "-pix_fmt", "yuv420p", "-s", f"{width}x{height}", "-y",
+               str(video_path)]
+        rc = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.STDOUT).returncode
+        if rc == 0:
+            result["video"] = str(video_path)
+            result["ffmpeg"] = "ok"
+        else:
+            result["ffmpeg"] = f"ffmpeg exited with status {rc}; the frames stay"
+    return result
+
+
 def make_video(extract, out_dir, video_path=None, band: int = 2, scene_scale: float = 1000.0,
                width: int = 640, height: int = 480, duration: float = 10.0,
                frame_rate: int = 60, settings: VolumeRenderSettings | None = None,
@@ -207,19 +231,4 @@ def make_video(extract, out_dir, video_path=None, band: int = 2, scene_scale: fl
             frames.append(str(out_dir / f"{f0 + k:06d}.ppm"))
             write_ppm(frames[-1], img)
     result = {"frames": frames, "shape": tuple(cube.shape), "video": None}
-    ffmpeg = shutil.which("ffmpeg")
-    if video_path is None:
-        result["ffmpeg"] = "not asked for (no video_path); the frames stay"
-    elif ffmpeg is None:
-        result["ffmpeg"] = "no ffmpeg binary on PATH; the frames stay"
-    else:
-        cmd = [ffmpeg, "-framerate", str(frame_rate), "-i", str(out_dir / "%06d.ppm"), "-c:v",
-               "libx264", "-pix_fmt", "yuv420p", "-s", f"{width}x{height}", "-y",
-               str(video_path)]
-        rc = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.STDOUT).returncode
-        if rc == 0:
-            result["video"] = str(video_path)
-            result["ffmpeg"] = "ok"
-        else:
-            result["ffmpeg"] = f"ffmpeg exited with status {rc}; the frames stay"
-    return result
+    return stitch_frames(result, out_dir, video_path, frame_rate, width, height)

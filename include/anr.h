@@ -54,7 +54,11 @@ extern "C" {
  *   - anr_voxel_traverse, anr_voxel_n_blocks, anr_voxel_count and anr_voxel_compact (the
  *     global-grid extract's exact voxel traversal into a bitmap and its ordered compaction);
  *   - anr_volume_render (the orbit video's single-scattering ray marcher over a dense
- *     density cube, with anr_camera and anr_volume_params).
+ *     density cube, with anr_camera and anr_volume_params);
+ *   - anr_sparse_volume_coarse_words, anr_sparse_volume_mark, anr_sparse_volume_popcount,
+ *     anr_sparse_volume_place, anr_sparse_volume_sample and anr_sparse_volume_render (the
+ *     global-grid extract's sparse volume -- bitmap, rank and ordered values -- and the same
+ *     march over it, with anr_sparse_volume).
  * ABI 4 (r06): anr_ingp_hash_field_fwd.
  * ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused field entry points' enc_stride < 0
  *   selecting the level-quad-plane layout it writes. */
@@ -592,6 +596,74 @@ typedef struct {
 int anr_volume_render(const float* density, int64_t nx, int64_t ny, int64_t nz,
                       const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
                       const anr_volume_params* params, float* rgba, anr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Global view of a global-grid extract: a sparse volume and the same march over it
+ * (csrc/sparse_volume.hip; the reference writes the global grid as a sparse OpenVDB file for
+ * an external viewer). The volume describes the box [0, ni) x [0, nj) x [0, nk) in
+ * box-relative indices: voxel (i, j, k) of the grid sits at position (i - i0, j - j0, k - k0).
+ * cells: (n_words, 2) uint32, n_words = row_pitch / 32 * nj * nk < 2^31, one {bits, rank}
+ * pair per word of the bitmap above (i fastest, row_pitch a multiple of 32 that is >= ni, bit
+ * b of word w of row (j, k) is voxel (32 w + b, j, k), pad bits 0); rank is the number of set
+ * bits in all words before it. values: (n_values) f32 in ascending bitmap order, so a present
+ * voxel's value is values[rank + popcount(bits & ((1 << b) - 1))]; 1 <= n_values < 2^31.
+ * coarse: anr_sparse_volume_coarse_words(ni, nj, nk) uint32 words, one bit per brick of
+ * 8 x 8 x 8 samples: brick (bi, bj, bk), bi fastest among (n >> 3) + 1 per axis, holds the
+ * samples with (floor(p) + 1) >> 3 = (bi, bj, bk) and is set if any present voxel v has v or
+ * v - 1 (per axis) as such a floor(p). A sample in an unset brick has all eight corners
+ * absent. coarse may be null when every call passes skip = 0.
+ * Build, in this order, on caller-zeroed cells and coarse; each call is independent of the
+ * order of the input voxels:
+ *   anr_sparse_volume_mark: voxels (n, 3) int32 grid indices, 1 <= n < 2^31; sets each voxel's
+ *     bit and its bricks. A voxel outside the box is not marked.
+ *   anr_sparse_volume_popcount: counts[w] (n_words, int32) = popcount(bits of word w); the
+ *     caller writes the exclusive prefix sum into the rank fields and refuses an input whose
+ *     total differs from n (a duplicate, or a voxel outside the box).
+ *   anr_sparse_volume_place: out[rank of voxel r] = values[r] * density_scale, the product in
+ *     f64 and rounded once to f32, NaN becoming 0 (VDB's background); values (n) f32.
+ * D(p) is anr_volume_render's: the trilinear interpolation of the eight voxels around
+ * floor(p) (z pairs, then y, then x, each a + w (b - a)), absent voxels and voxels outside the
+ * box being 0, so D vanishes outside [-1, n_d] per axis.
+ * anr_sparse_volume_sample: positions (P, 3) f32 box-relative -> out (P) f32 D(p); NaN and
+ * far-away positions give 0.
+ * anr_sparse_volume_render: cameras (box-relative coordinates), params, rgba and every
+ * refusal as anr_volume_render, except that no byte limit applies to the box. The output
+ * equals, bit for bit, anr_volume_render on the densified cube ((ni, nj, nk) f32, zeros where
+ * no voxel is): the march is the same code, and every t comes from the step index.
+ * skip 1: a sample in an unset brick returns +0.0 without its eight lookups, which is the
+ * value they give; 0: every sample looks its corners up (same output; for tests and timing).
+ * counters: null, or two int64 in DEVICE memory, added to (the caller zeroes them): [0]
+ * samples whose floor(p) lies in [-1, n - 1] on every axis, [1] those of them the coarse level
+ * answered. volume is a HOST struct, read during the call. ANR_E_INVALID, before any launch:
+ * a null pointer, an extent < 1, a bad row_pitch, 2^31 words or bricks or more, n_values
+ * outside [1, 2^31), skip other than 0 or 1. P = 0 or F * H * W = 0: ANR_OK without a launch.
+ * Nothing here allocates or synchronises. ------------------------------------------------ */
+typedef struct {
+  const uint32_t* cells; /* DEVICE (n_words, 2) {bits, rank} */
+  const float* values;   /* DEVICE (n_values) */
+  const uint32_t* coarse; /* DEVICE brick bits, or null (skip = 0 only) */
+  int32_t ni, nj, nk;
+  int32_t reserved; /* 0 */
+  int64_t row_pitch;
+  int64_t n_values;
+} anr_sparse_volume;
+int64_t anr_sparse_volume_coarse_words(int32_t ni, int32_t nj, int32_t nk);
+int anr_sparse_volume_mark(const int32_t* voxels, int64_t n, int32_t i0, int32_t j0, int32_t k0,
+                           int32_t ni, int32_t nj, int32_t nk, int64_t row_pitch,
+                           uint32_t* cells, uint32_t* coarse, anr_stream_t stream);
+int anr_sparse_volume_popcount(const uint32_t* cells, int64_t n_words, int32_t* counts,
+                               anr_stream_t stream);
+int anr_sparse_volume_place(const int32_t* voxels, const float* values, int64_t n,
+                            double density_scale, int32_t i0, int32_t j0, int32_t k0, int32_t ni,
+                            int32_t nj, int32_t nk, int64_t row_pitch, const uint32_t* cells,
+                            int64_t n_values, float* out, anr_stream_t stream);
+int anr_sparse_volume_sample(const anr_sparse_volume* volume, int32_t skip,
+                             const float* positions, int64_t P, float* out,
+                             anr_stream_t stream);
+int anr_sparse_volume_render(const anr_sparse_volume* volume, int32_t skip,
+                             const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
+                             const anr_volume_params* params, float* rgba, int64_t* counters,
+                             anr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * NeRF path (configs/nerf.json): positional encoding (encoders.py:4-28) and the

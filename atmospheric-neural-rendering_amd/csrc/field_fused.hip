@@ -428,28 +428,9 @@ __device__ __forceinline__ void fma_h4(float (&acc)[4], h4 x, uint32_t d2) {
   }
 }
 
-// Reference numerics: the gradient tiles hold tcnn's loss-scaled f16 values, many of them
-// deep in f16's subnormal range, and v_mfma_f32_16x16x32_f16 sums products of deeply
-// subnormal f16 operands inexactly (a single product is exact; 64-term sums of operands
-// ~2^-20 come out 28,844 f32 ulps rms from the exact sum against 62 for an f32 loop, with
-// a bias toward zero: tools/r5/mfma_precision.py, profiles/r05_mfma_precision.log). The
-// input-gradient products therefore take the subnormal part of the gradient operand
-// separately, scaled by 2^10 into the normal range (exact: a power of two, and every
-// subnormal times 2^10 stays below 1/16): W g = W g_normal + 2^-10 W (2^10 g_subnormal).
-// The split is exact and the two f32 partial sums are added once. (The dW products keep
-// the plain operand: their sums are dominated by the normal-range gradients.)
-#ifndef ANR_REF_SPLIT
-#define ANR_REF_SPLIT 0
-#endif
-typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split_sub(h4 g, h4& gn, h4& gs) {
-  const u16x4 b = __builtin_bit_cast(u16x4, g);
-  const u16x4 z = {0, 0, 0, 0};
-  const u16x4 sub = (b & u16x4{0x7C00, 0x7C00, 0x7C00, 0x7C00}) == z ? b : z;  // exp field 0
-  gn = __builtin_bit_cast(h4, b ^ sub);
-  const _Float16 k = static_cast<_Float16>(1024.0f);
-  gs = __builtin_bit_cast(h4, sub) * h4{k, k, k, k};
-}
+// Reference numerics: splitting the subnormal part off the gradient operand of the dX MFMAs
+// (v_mfma_f32_16x16x32_f16 sums deeply subnormal products inexactly) was measured and
+// reverted (+0.4 ms): profiles/r05_mfma_precision.log, DESIGN section 11, item 3.
 
 // Global inputs of one 16-sample half-tile for this lane, loaded a tile ahead.
 struct Rows {
@@ -1534,49 +1515,87 @@ __device__ __forceinline__ h4 tr_b(h8 x, h8 sel) {
 }
 
 
-// REF (reference numerics, f16 only): the gradient scale is tcnn's fixed loss scale
-// (a.loss_scale = 128) instead of the per-wavefront power of two, the ReLU masks test the
-// f16-rounded outputs, and the gradients that cross tinycudann module boundaries in the
-// reference are rounded as they are there: dL/dpos_out[1:16] comes back from dir_mlp /
-// dir_encoder as f16(f16(g_scaled) / 128) (an f16 division that keeps subnormals, as
-// torch's does: tests/test_field_ref16_oracle_gpu.py) and is
-// rescaled for pos_mlp, and dL/denc is written as f16(f16(g_scaled) / 128)
-// (tinycudann/modules.py: input_grad / loss_scale, cast to the f16 input's dtype).
-// REF 2 (anr_ingp_field_bwd_ref16_rows): the same arithmetic, dL/denc written as f16 (its
-// values are f16 numbers already, so the rows hold them exactly) plus one bit per row, set
-// when any of the row's 32 values is nonzero (a.row_nz, one 32-bit word per 32-row tile)
-// REF 4 (the pos pass of anr_ingp_field_bwd_ref16_rows with a workspace): REF 2 on the
-// tiles whose dL/dcolor is zero in every row -- the pos network only, so the dir network's
-// registers, dW accumulators and LDS sums are not part of the kernel and more waves fit a
-// SIMD -- while a tile with a nonzero dL/dcolor is appended to a.tile_list (a.tile_count)
-// and left alone. Its output layer is rank 1 (see w1r in the kernel), its dL/denc rows stay
-// f16 from the accumulator to the store, and its zero tests read the f16 bits: the pass is
-// bound by VALU issue (profiles/pos_rank1_summary.md); same dL/denc, row bits and list as
-// REF 2, g_pos up to the f32 order of row 0 of dW_P1.
-// REF 3 (the list pass, launched after it): REF 2 on exactly the listed
-// tiles (count read on the device), the whole network.
-// HG (anr_ingp_field_bwd_ref16_rows_h, REF 2 / 3 / 4): dL/dsigma and dL/dcolor arrive as the
-// f16 values the f16 composite backward writes (10 B per row instead of 20) and are
-// converted to f32 as they are loaded; everything after the load is the f32 form's code.
-// S > 1 (build numerics, dense rows): d_sigma is (M, S); dL/dpos_out[j < S] is d_sigma[j]
-// through unit j's own ReLU (the dir network has no input from those units: zero rows in
-// its transposed first-layer fragments), all in the g == 0 lane's four registers.
-template <int W, int NHD, bool FAST, bool ROWS, bool BF, int REF = 0, bool HG = false, int S = 1>
+// ---- forms of the backward kernel: bwd_rt_kernel<W, NHD, BF, S, F> is compiled for a form F
+// that names its numerics, what it writes dL/denc as, which pass it is and how its inputs
+// arrive. The entry points and plan_bwd / plan_bwd_ref pick forms by these names.
+enum class Pass { whole, pos, list };
+struct GeneralColor : std::false_type {};  // dL/dcolor of any n_out / stride, d_sigma nullable
+struct FastColor : std::true_type {};      // n_out == 4, aligned rows, d_sigma: prefetched a tile ahead
+struct DenseRows : std::false_type {};     // row r is sample r
+struct GatheredRows : std::true_type {};   // row r is sample a.rows[r] (occupancy-compacted)
+struct F32Grads : std::false_type {};      // a.d_sigma / a.d_color
+struct F16Grads : std::true_type {};       // a.d_sigma_h / a.d_color_h, as the f16 composite backward
+                                           // writes them (10 B per row instead of 20); converted to
+                                           // f32, exactly, as they are loaded
+template <bool REF_, bool RMASK_, Pass PASS_, typename Grads, typename Rows, typename Color>
+struct Form {
+  // Reference numerics (tcnn's loss-scaled f16 backward, f16 only): the gradient scale is the
+  // fixed a.loss_scale instead of the per-wavefront power of two, the ReLU masks test the
+  // f16-rounded outputs, and the gradients that cross tinycudann module boundaries are rounded
+  // as they are there: dL/dpos_out[1:16] comes back from dir_mlp as f16(f16(g_scaled) / scale)
+  // (an f16 division that keeps subnormals, as torch's does:
+  // tests/test_field_ref16_oracle_gpu.py) and is rescaled for pos_mlp, and dL/denc is written
+  // as f16(f16(g_scaled) / scale) (tinycudann/modules.py: input_grad / loss_scale in the f16
+  // input's dtype). Build numerics otherwise.
+  static constexpr bool REF = REF_;
+  // dL/denc as f16 rows (a.d_enc_h; the values are f16 numbers already) plus one bit per row,
+  // set when any of the row's 32 values is nonzero (a.row_nz, a word per 32-row tile);
+  // f32 rows (a.d_enc) otherwise
+  static constexpr bool RMASK = RMASK_;
+  static constexpr Pass PASS = PASS_;
+  static constexpr bool POS = PASS == Pass::pos;    // no dir network in this kernel
+  static constexpr bool LIST = PASS == Pass::list;  // walks a.tile_list, the general tile path
+  static constexpr bool HG = Grads::value, ROWS = Rows::value, FAST = Color::value;
+  // full tiles of the pos pass with f16 gradients: "any dL/dcolor nonzero" from the raw bits
+  static constexpr bool RAWC = POS && HG;
+  static_assert(!HG || RMASK, "f16 gradients: the reference-numerics f16-rows forms");
+  static_assert(!RMASK || REF, "f16 rows and row bits: reference numerics");
+  static_assert(PASS == Pass::whole || (RMASK && FAST),
+                "the pos / list passes write f16 rows and use the fast d_color layout");
+  static_assert(!(REF && ROWS), "reference numerics: dense rows");
+  // the forms a numeric type BF and S density outputs exist for
+  template <bool BF, int S>
+  static constexpr bool fits() {
+    static_assert(!(REF && BF), "reference numerics are f16");
+    static_assert(S == 1 || (!REF && !ROWS), "S > 1: build numerics, dense rows");
+    return true;
+  }
+};
+// build numerics: per-wavefront dynamic scale, f32 gradients and rows. S > 1 (dense rows):
+// d_sigma is (M, S); dL/dpos_out[j < S] is d_sigma[j] through unit j's own ReLU (the dir network
+// has no input from those units), all in the g == 0 lane's four registers
+template <typename Color, typename Rows>
+struct Build : Form<false, false, Pass::whole, F32Grads, Rows, Color> {};
+// anr_ingp_field_bwd_ref16: reference numerics, dL/denc as f32 rows
+template <typename Color>
+struct RefF32Rows : Form<true, false, Pass::whole, F32Grads, DenseRows, Color> {};
+// anr_ingp_field_bwd_ref16_rows (_h: F16Grads) without a workspace: f16 rows and row bits
+template <typename Color, typename Grads>
+struct RefF16Rows : Form<true, true, Pass::whole, Grads, DenseRows, Color> {};
+// its pos pass, with a workspace: RefF16Rows on the tiles whose dL/dcolor is zero in every row,
+// the pos network only (no dir registers, dW accumulators or LDS sums: more waves fit a SIMD);
+// a tile with a nonzero dL/dcolor is appended to a.tile_list and left alone. Rank-1 output
+// layer (w1r), f16 dL/denc from accumulator to store, zero tests on the f16 bits: bound by VALU
+// issue (profiles/pos_rank1_summary.md). Same dL/denc, row bits and list as RefF16Rows, g_pos
+// up to the f32 order of row 0 of dW_P1
+template <typename Grads>
+struct PosPass : Form<true, true, Pass::pos, Grads, DenseRows, FastColor> {};
+// the list pass, launched after it: RefF16Rows on exactly the listed tiles (count read on the
+// device), the whole network
+template <typename Grads>
+struct ListPass : Form<true, true, Pass::list, Grads, DenseRows, FastColor> {};
+
+template <int W, int NHD, bool BF, int S, typename F>
 __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64_t tpw,
                                                      const float* wmax) {
-  static_assert(!(REF && BF), "reference numerics are f16");
-  static_assert(!HG || REF >= 2, "f16 gradients: the reference-numerics f16-rows forms");
-  static_assert(S == 1 || (REF == 0 && !ROWS), "S > 1: build numerics, dense rows");
-  using RawRows = RawRowsT<HG, S>;
-  static_assert(REF < 3 || FAST, "the pos / list passes use the fast d_color layout");
-  constexpr bool RMASK = REF >= 2;
-  constexpr bool POS = REF == 4;  // no dir network in this kernel
+  static_assert(F::template fits<BF, S>(), "no such backward kernel");
+  using RawRows = RawRowsT<F::HG, S>;
   // MT 16-sample halves per tile, the dW contraction over NP pairs of them. (64-sample
   // tiles, MT = 4, measured 6 % slower at the same 1 wave/SIMD: profiles/r03_field_bwd_ab.log)
   constexpr int MT = 2, TR = 16 * MT, NP = MT / 2;
   using N = Net<W, NHD, S>;
   constexpr int NT = N::NT, KB = N::KB;
-  if constexpr (REF == 3) {
+  if constexpr (F::LIST) {
     // the list pass: a block none of whose waves has a listed tile leaves before its
     // prologue (weights into LDS, sums zeroed): in the settled state the list is empty and
     // the whole launch was ~26 us of prologues (rocprof r06_c). Block-uniform exit.
@@ -1587,12 +1606,12 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   __shared__ __attribute__((aligned(16))) _Float16 wsm[N::n_packed];
   // the block's dW partials (pos parameters, then dir), summed here before the one global
   // flush per block
-  __shared__ float red[POS ? N::NPOS : N::NPOS + N::NDIR];
+  __shared__ float red[F::POS ? N::NPOS : N::NPOS + N::NDIR];
   const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
   const int waves = blockDim.x >> 6, wave = threadIdx.x >> 6;
   for (int e = threadIdx.x * 8; e < N::n_packed; e += blockDim.x * 8)
     *reinterpret_cast<h8*>(wsm + e) = *reinterpret_cast<const h8*>(a.packed + e);
-  constexpr int NRED = POS ? N::NPOS : N::NPOS + N::NDIR;
+  constexpr int NRED = F::POS ? N::NPOS : N::NPOS + N::NDIR;
   for (int e = threadIdx.x; e < NRED; e += blockDim.x) red[e] = 0.0f;
   __syncthreads();
   // per-tile opaque copy of the fragment base: the weight fragments are re-read from LDS
@@ -1602,14 +1621,12 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   auto bfrag16 = [&](int off) { return *reinterpret_cast<const h4*>(wbt + off + lane * 4); };
   TrConst<BF> tc;
   tc.init(lane);
-  // dW operand transposes (MFMA against the constant 0/1 operands); the slot argument
-  // names the r03 LDS image of the removed LT generation and is unused
-  auto trc = [&](int, h4 x) -> h4 { return tr_c<BF>(x, tc.id); };
-  auto trb = [&](int, h8 x, h4& o0, h4& o1) {
+  // dW operand transposes (MFMA against the constant 0/1 operands)
+  auto trc = [&](h4 x) -> h4 { return tr_c<BF>(x, tc.id); };
+  auto trb = [&](h8 x, h4& o0, h4& o1) {
     o0 = tr_b<BF>(x, tc.sel[0]);
     o1 = tr_b<BF>(x, tc.sel[1]);
   };
-  constexpr int R0 = 0, R1 = 16;
   // POS: dL/dpos_out is dL/dsigma in unit 0 and exact zeros in the other 15 units, so the
   // output layer's backward is rank 1: dhp = P1[0][:] * dpo0 (one f16 product per value,
   // what the MFMA's single nonzero term rounded to f16 is) and only row 0 of dW_P1 gets
@@ -1618,7 +1635,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   // in f32 over the lane's samples and reduced over the 16 sample lanes after the loop.
   h4 w1r[NT];
   float dP1r[NT][4];
-  if constexpr (POS) {
+  if constexpr (F::POS) {
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
@@ -1646,7 +1663,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     for (int i = 0; i < NT * NT; ++i) dD1[i] = z4;
   }
   float s = 1.0f, inv_s = 1.0f;
-  if constexpr (REF) {
+  if constexpr (F::REF) {
     s = a.loss_scale;
     inv_s = 1.0f / a.loss_scale;
   } else if constexpr (!BF) {
@@ -1660,37 +1677,6 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   }
   // f32 -> f16 -> f32 (the reference's f16 tensors between modules)
   auto r16 = [](float v) { return static_cast<float>(static_cast<_Float16>(v)); };
-  // input-gradient products (REF: subnormal part of the gradient operand split off, see
-  // split_sub); dx32 accumulates the K blocks of one product into (acc, accs), dx_join
-  // adds the two partial sums
-  constexpr bool SPLIT = REF && ANR_REF_SPLIT;
-  auto dx16 = [&](h4 w, h4 gg) -> f4 {
-    if constexpr (SPLIT) {
-      h4 gn, gs;
-      split_sub(gg, gn, gs);
-      return mma16<BF>(w, gn, z4) + mma16<BF>(w, gs, z4) * 0x1p-10f;
-    } else {
-      return mma16<BF>(w, gg, z4);
-    }
-  };
-  auto dx32 = [&](h8 w, h4 g0, h4 g1, f4& acc, f4& accs) {
-    if constexpr (SPLIT) {
-      h4 n0, s0, n1, s1;
-      split_sub(g0, n0, s0);
-      split_sub(g1, n1, s1);
-      acc = mma32<BF>(w, cat(n0, n1), acc);
-      accs = mma32<BF>(w, cat(s0, s1), accs);
-    } else {
-      acc = mma32<BF>(w, cat(g0, g1), acc);
-    }
-  };
-  auto dx_join = [&](f4 (&acc)[MT], const f4 (&accs)[MT]) {
-    if constexpr (SPLIT) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt] += accs[mt] * 0x1p-10f;
-    }
-  };
-
   Rows cur[MT];
   f4 curb[S > 1 ? MT : 1];  // S > 1: dL/dsigma[row][0 .. S-1] of cur's rows
   // the next tile's raw inputs, loaded a tile ahead into alternating register sets (the
@@ -1699,10 +1685,10 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   // early in the tile it waits on the loads just issued (1 wave/SIMD: nothing hides it)
   RawRows nr0[MT], nr1[MT];
   const int64_t t_full_end = t_end < n_full ? t_end : n_full;
-  if constexpr (FAST) {
+  if constexpr (F::FAST) {
     if (t_begin < t_full_end) {
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS, HG, S>(a, t_begin * TR + mt * 16 + li, g, nr0[mt]);
+      for (int mt = 0; mt < MT; ++mt) load_raw<F::ROWS, F::HG, S>(a, t_begin * TR + mt * 16 + li, g, nr0[mt]);
       // drained once, so the loop entry carries no pending loads: entered with the first
       // prefetch in flight, the waitcnt pass merges that state with the back edge's (the
       // prefetch, then the tile's d_enc stores) into a wait for everything, stores
@@ -1734,7 +1720,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   const bool inv_is_h = static_cast<float>(inv_h) == inv_s;
   // one lane's 4 values of dL/denc row `row`, columns 16 kt + 4 g .. + 3
   auto put = [&](int64_t row, int kt, const f4& v) {
-    if constexpr (RMASK) {
+    if constexpr (F::RMASK) {
       const h4 hv = {static_cast<_Float16>(v[0]), static_cast<_Float16>(v[1]),
                      static_cast<_Float16>(v[2]), static_cast<_Float16>(v[3])};
       *reinterpret_cast<h4*>(a.d_enc_h + row * a.d_enc_stride + 16 * kt + 4 * g) = hv;
@@ -1746,7 +1732,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   // zero" (uniform control flow: the ballots need every lane); rows of a row's four lanes
   // g = 0..3 sit at ballot bits li + 16 g
   auto put_mask = [&](int64_t tile, const bool (&nz)[MT]) {
-    if constexpr (RMASK) {
+    if constexpr (F::RMASK) {
       uint32_t word = 0;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -1762,7 +1748,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
            v1[1] != 0.0f || v1[2] != 0.0f || v1[3] != 0.0f;
   };
   auto store_pend = [&]() {
-    if constexpr (POS) {
+    if constexpr (F::POS) {
       typedef uint32_t u2 __attribute__((ext_vector_type(2)));
       bool nz[MT];
 #pragma unroll
@@ -1781,13 +1767,43 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) put(pend_tile * TR + mt * 16 + li, kt, pend[kt][mt]);
-    if constexpr (RMASK) {
+    if constexpr (F::RMASK) {
       bool nz[MT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) nz[mt] = nz_of(pend[0][mt], pend[1][mt]);
       put_mask(pend_tile, nz);
     }
   };
+  // the dW MFMAs issued so far have written their accumulators before anything (a loop-exit
+  // copy) reads them
+  auto fence = [&]() {
+    agpr_fence();
+    if constexpr (!F::POS) {
+      agpr_pin(dD2);
+      agpr_pin(dD1);
+      agpr_pin(dD0);
+      agpr_pin(dP1);
+    }
+    agpr_pin(dP0);
+  };
+  // dX of a layer, one 16-unit block: the layer's KB K blocks of W^T (fragments w[kb]) times
+  // the gradient tiles gr
+  auto dx_block = [&](const h8* w, const h4(&gr)[MT][NT], f4(&dx)[MT]) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) dx[mt] = z4;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+        dx[mt] = mma32<BF>(w[kb], cat(gr[mt][2 * kb], gr[mt][2 * kb + 1]), dx[mt]);
+    }
+  };
+  // One tile, as eight steps: 1 the tile head, 2 the gradient-free exit, 3 the colour-free
+  // decision and the list append, 4 the forward recompute, 5 the dir network's backward, 6 the
+  // pos output layer, 7 the pos input layer with the dL/denc emit; 8, the dW flush, ends the
+  // kernel. (A step as a function or lambda of its own changes the machine code, see DESIGN
+  // section 5 "Forms", so they stay one body.) nraw holds the tile's prefetched inputs, nnext
+  // takes the next tile's (FAST full tiles).
   auto process = [&](auto full_c, int64_t tile, RawRows(&nraw)[MT], RawRows(&nnext)[MT]) {
     constexpr bool FULL = decltype(full_c)::value;
     {
@@ -1797,9 +1813,10 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     }
     // POS, f16 gradients, full tiles: "any dL/dcolor nonzero" from the raw bits of the row's
     // four f16 values (every lane group loaded the same four), not from eight f32 compares
-    constexpr bool RAWC = POS && HG && FAST && FULL;
+    constexpr bool RAWC = F::RAWC && FULL;
     uint32_t dcor = 0;
-    if constexpr (FAST && FULL) {
+    // ---- 1, the tile's inputs
+    if constexpr (F::FAST && FULL) {
       // the tile's head: this tile's prefetched inputs are converted here (hoisted into the
       // previous tile, the conversion waits on loads just issued) and the next tile's loads
       // are issued here (the scheduler otherwise sinks them toward the tile's end)
@@ -1834,21 +1851,21 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       store_pend();
       const int64_t tn = tile + 1 < t_full_end ? tile + 1 : tile;
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) load_raw<ROWS, HG, S>(a, tn * TR + mt * 16 + li, g, nnext[mt]);
+      for (int mt = 0; mt < MT; ++mt) load_raw<F::ROWS, F::HG, S>(a, tn * TR + mt * 16 + li, g, nnext[mt]);
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        load_rows<ROWS, HG, S>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
+        load_rows<F::ROWS, F::HG, S>(a, tile * TR + mt * 16 + li, g, true, cur[mt]);
       if constexpr (S > 1) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-          curb[mt] = load_dsig<ROWS, S>(a, tile * TR + mt * 16 + li);
+          curb[mt] = load_dsig<F::ROWS, S>(a, tile * TR + mt * 16 + li);
       }
     }
     const bool full = FULL;
     {
-      // A tile whose incoming gradients (dL/dcolor, dL/dsigma) are zero in every row adds
+      // ---- 2. A tile whose incoming gradients (dL/dcolor, dL/dsigma) are zero in every row adds
       // exactly nothing to dW and has dL/denc = 0: store the zeros, skip the recompute and
       // the backward (wave-uniform). Under the reference numerics tcnn's x128 f16 backward
       // leaves most tiles so once training settles (profiles/r05_state160.log); the build
@@ -1869,7 +1886,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       if (a.tile_nz && lane == 0) a.tile_nz[tile] = walk ? 1 : 0;
       if (!walk) {
         const f4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (FAST && FULL) {
+        if constexpr (F::FAST && FULL) {
 #pragma unroll
           for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -1888,7 +1905,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
             for (int kt = 0; kt < 2; ++kt) put(row, kt, zero4);
           }
         }
-        if constexpr (RMASK) {
+        if constexpr (F::RMASK) {
           bool nz[MT];
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) nz[mt] = false;
@@ -1897,7 +1914,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         return;
       }
     }
-    // A tile whose dL/dcolor is zero in every row (reference numerics: every tile once
+    // ---- 3. A tile whose dL/dcolor is zero in every row (reference numerics: every tile once
     // training settles -- tcnn's f16 composite backward rounds the per-sample colour
     // gradients of the atmosphere's tiny weights to zero, profiles/r05_hash_bwd_state_tiles
     // .log): the dir network's backward adds exactly 0 to its dW and returns dX = 0, so
@@ -1910,7 +1927,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     bool dir_walk = true;
     if constexpr (RAWC) {
       dir_walk = __any((dcor & 0x7FFF7FFFu) != 0u);
-    } else if constexpr (REF && FAST) {
+    } else if constexpr (F::REF && F::FAST) {
       bool cnz = false;
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -1918,13 +1935,13 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
               cur[mt].dc[3] != 0.0f;
       dir_walk = __any(cnz);
     }
-    if constexpr (POS) {
+    if constexpr (F::POS) {
       if (dir_walk) {  // the list pass takes this tile (d_enc rows and bits included)
         if (lane == 0) a.tile_list[atomicAdd(a.tile_count, 1u)] = static_cast<int32_t>(tile);
         return;
       }
     }
-    // ---- forward recompute of both 16-sample halves; every activation stays in registers
+    // ---- 4, forward recompute of both 16-sample halves; every activation stays in registers
     Tile<W, NHD> t[MT];
     h4 gc[MT];
     bool dens[MT];
@@ -1934,11 +1951,11 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) valid[mt] = full || tile * TR + mt * 16 + li < a.M;
       FwdWeights<W, NHD> fwl;
-      fwl.load(wbt, lane, !POS && dir_walk);
-      tile_forward<W, NHD, MT, BF, S>(fwl, cur, valid, g, t, NoSink{}, !POS && dir_walk);
+      fwl.load(wbt, lane, !F::POS && dir_walk);
+      tile_forward<W, NHD, MT, BF, S>(fwl, cur, valid, g, t, NoSink{}, !F::POS && dir_walk);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        dens[mt] = (REF ? r16(t[mt].po[0]) : t[mt].po[0]) > 0.0f;
+        dens[mt] = (F::REF ? r16(t[mt].po[0]) : t[mt].po[0]) > 0.0f;
         if constexpr (S > 1) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) densb[mt][j] = t[mt].po[j] > 0.0f;
@@ -1946,14 +1963,14 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         f4 gv;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          gv[i] = (REF ? r16(t[mt].col[i]) : t[mt].col[i]) > 0.0f ? cur[mt].dc[i] * s : 0.0f;
+          gv[i] = (F::REF ? r16(t[mt].col[i]) : t[mt].col[i]) > 0.0f ? cur[mt].dc[i] * s : 0.0f;
         gc[mt] = to_h4<BF>(gv);
       }
     }
     h4 dpo[MT];
-    if (!POS && dir_walk) {
+    if (!F::POS && dir_walk) {
       auto last = [&](int mt, int kt) -> h4 { return NHD == 2 ? t[mt].hd1[kt] : t[mt].hd0[kt]; };
-      // ---- dir output layer: dW_D2 (16 x W) += gc^T · X_last ; dX_last = D2^T gc
+      // ---- 5, the dir network. dir output layer: dW_D2 (16 x W) += gc^T · X_last ; dX_last = D2^T gc
       // Each layer's W^T fragments are read from LDS at the start of the layer and pinned
       // there (sched_barrier): the dW half of the layer, which needs no weights, then covers
       // the LDS latency that a read placed at its use exposes (1 wave/SIMD).
@@ -1966,16 +1983,16 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         h8 ga[NP];
   #pragma unroll
         for (int pr = 0; pr < NP; ++pr)
-          ga[pr] = cat(trc(R0 + 0, gc[2 * pr]), trc(R0 + 1, gc[2 * pr + 1]));
+          ga[pr] = cat(trc(gc[2 * pr]), trc(gc[2 * pr + 1]));
   #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
   #pragma unroll
           for (int pr = 0; pr < NP; ++pr) {
-            const h8 xl = cat(trc(R0 + 2 + 2 * kt, last(2 * pr, kt)), trc(R0 + 3 + 2 * kt, last(2 * pr + 1, kt)));
+            const h8 xl = cat(trc(last(2 * pr, kt)), trc(last(2 * pr + 1, kt)));
             mma32_acc_v<BF>(dD2[kt], ga[pr], xl);
           }
   #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) dl[mt][kt] = mask_h4<BF>(dx16(wd2[kt], gc[mt]), last(mt, kt));
+          for (int mt = 0; mt < MT; ++mt) dl[mt][kt] = mask_h4<BF>(mma16<BF>(wd2[kt], gc[mt], z4), last(mt, kt));
         }
       }
       // ---- dir hidden layer 1 (NHD == 2): dW_D1 (W x W) += dl^T · X_d0 ; dh0 = D1^T dl
@@ -1990,26 +2007,18 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
           h8 gb[NT];
   #pragma unroll
           for (int nt = 0; nt < NT; ++nt)
-            gb[nt] = cat(trc(R1 + 2 * nt, dl[2 * pr][nt]), trc(R1 + 1 + 2 * nt, dl[2 * pr + 1][nt]));
+            gb[nt] = cat(trc(dl[2 * pr][nt]), trc(dl[2 * pr + 1][nt]));
   #pragma unroll
           for (int kt = 0; kt < NT; ++kt) {
-            const h8 xb = cat(trc(R1 + 8 + 2 * kt, t[2 * pr].hd0[kt]), trc(R1 + 9 + 2 * kt, t[2 * pr + 1].hd0[kt]));
+            const h8 xb = cat(trc(t[2 * pr].hd0[kt]), trc(t[2 * pr + 1].hd0[kt]));
   #pragma unroll
             for (int nt = 0; nt < NT; ++nt) mma32_acc_v<BF>(dD1[nt * NT + kt], gb[nt], xb);
           }
         }
   #pragma unroll
         for (int kt = 0; kt < NT; ++kt) {
-          f4 acc[MT], accs[MT];
-  #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) acc[mt] = accs[mt] = z4;
-  #pragma unroll
-          for (int kb = 0; kb < KB; ++kb) {
-  #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              dx32(wd1[kt * KB + kb], dl[mt][2 * kb], dl[mt][2 * kb + 1], acc[mt], accs[mt]);
-          }
-          dx_join(acc, accs);
+          f4 acc[MT];
+          dx_block(wd1 + kt * KB, dl, acc);
   #pragma unroll
           for (int mt = 0; mt < MT; ++mt) dh0[mt][kt] = mask_h4<BF>(acc[mt], t[mt].hd0[kt]);
         }
@@ -2028,28 +2037,21 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   #pragma unroll
         for (int pr = 0; pr < NP; ++pr) {
           h4 a0, a1, b0, b1;
-          trb(R0 + 0, t[2 * pr].xd, a0, a1);
-          trb(R0 + 2, t[2 * pr + 1].xd, b0, b1);
+          trb(t[2 * pr].xd, a0, a1);
+          trb(t[2 * pr + 1].xd, b0, b1);
           const h8 x0 = cat(a0, b0), x1 = cat(a1, b1);
   #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
-            const h8 gd = cat(trc(R0 + 4 + 2 * nt, dh0[2 * pr][nt]), trc(R0 + 5 + 2 * nt, dh0[2 * pr + 1][nt]));
+            const h8 gd = cat(trc(dh0[2 * pr][nt]), trc(dh0[2 * pr + 1][nt]));
             mma32_acc_v<BF>(dD0[nt * 2], gd, x0);
             mma32_acc_v<BF>(dD0[nt * 2 + 1], gd, x1);
           }
         }
-        f4 acc[MT], accs[MT];
-  #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = accs[mt] = z4;
-  #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-  #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) dx32(wd0[kb], dh0[mt][2 * kb], dh0[mt][2 * kb + 1], acc[mt], accs[mt]);
-        }
-        dx_join(acc, accs);
+        f4 acc[MT];
+        dx_block(wd0, dh0, acc);
   #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          if constexpr (REF) {
+          if constexpr (F::REF) {
   #pragma unroll
             for (int i = 0; i < 4; ++i) acc[mt][i] = r16(r16(r16(acc[mt][i]) * inv_s) * s);
           }
@@ -2068,7 +2070,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
           dpo[mt] = to_h4<BF>(acc[mt]);
         }
       }
-    } else if constexpr (!POS) {
+    } else if constexpr (!F::POS) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         f4 acc = z4;
@@ -2076,9 +2078,9 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         dpo[mt] = to_h4<BF>(acc);
       }
     }
-    // ---- pos output layer: dW_P1 (16 x W) += dpo^T · X_ph ; dhp = P1^T dpo
+    // ---- 6, pos output layer: dW_P1 (16 x W) += dpo^T · X_ph ; dhp = P1^T dpo
     h4 dhp[MT][NT];
-    if constexpr (POS) {
+    if constexpr (F::POS) {
       // rank 1 (see w1r): dpo0 = f16(dL/dsigma * scale) through the density ReLU, formed in
       // the row's g == 0 lane (the one holding pos_out[0]) and handed to its other three
       // lane groups, both halves of the tile in one 32-bit word
@@ -2105,19 +2107,19 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       h8 ga[NP];
 #pragma unroll
       for (int pr = 0; pr < NP; ++pr)
-        ga[pr] = cat(trc(R1 + 0, dpo[2 * pr]), trc(R1 + 1, dpo[2 * pr + 1]));
+        ga[pr] = cat(trc(dpo[2 * pr]), trc(dpo[2 * pr + 1]));
 #pragma unroll
       for (int kt = 0; kt < NT; ++kt) {
 #pragma unroll
         for (int pr = 0; pr < NP; ++pr) {
-          const h8 xp = cat(trc(R1 + 2 + 2 * kt, t[2 * pr].hp[kt]), trc(R1 + 3 + 2 * kt, t[2 * pr + 1].hp[kt]));
+          const h8 xp = cat(trc(t[2 * pr].hp[kt]), trc(t[2 * pr + 1].hp[kt]));
           mma32_acc_v<BF>(dP1[kt], ga[pr], xp);
         }
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) dhp[mt][kt] = mask_h4<BF>(dx16(wp1[kt], dpo[mt]), t[mt].hp[kt]);
+        for (int mt = 0; mt < MT; ++mt) dhp[mt][kt] = mask_h4<BF>(mma16<BF>(wp1[kt], dpo[mt], z4), t[mt].hp[kt]);
       }
     }
-    // ---- pos input layer: dW_P0 (W x 32) += dhp^T · X_pe ; d_enc = P0^T dhp
+    // ---- 7, pos input layer: dW_P0 (W x 32) += dhp^T · X_pe ; d_enc = P0^T dhp
     {
       h8 wp0[2 * KB];
 #pragma unroll
@@ -2126,34 +2128,26 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
 #pragma unroll
       for (int pr = 0; pr < NP; ++pr) {
         h4 a0, a1, b0, b1;
-        trb(R0 + 0, t[2 * pr].xe, a0, a1);
-        trb(R0 + 2, t[2 * pr + 1].xe, b0, b1);
+        trb(t[2 * pr].xe, a0, a1);
+        trb(t[2 * pr + 1].xe, b0, b1);
         const h8 x0 = cat(a0, b0), x1 = cat(a1, b1);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-          const h8 gp = cat(trc(R0 + 4 + 2 * nt, dhp[2 * pr][nt]), trc(R0 + 5 + 2 * nt, dhp[2 * pr + 1][nt]));
+          const h8 gp = cat(trc(dhp[2 * pr][nt]), trc(dhp[2 * pr + 1][nt]));
           mma32_acc_v<BF>(dP0[nt * 2], gp, x0);
           mma32_acc_v<BF>(dP0[nt * 2 + 1], gp, x1);
         }
       }
       // RMASK outside the pend path: the tile's rows, kept until both column halves are out
-      f4 keep[RMASK && !(FAST && FULL) ? 2 : 1][MT];
+      f4 keep[F::RMASK && !(F::FAST && FULL) ? 2 : 1][MT];
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
-        f4 acc[MT], accs[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = accs[mt] = z4;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-            dx32(wp0[kt * KB + kb], dhp[mt][2 * kb], dhp[mt][2 * kb + 1], acc[mt], accs[mt]);
-        }
-        dx_join(acc, accs);
+        f4 acc[MT];
+        dx_block(wp0 + kt * KB, dhp, acc);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const int64_t row = tile * TR + mt * 16 + li;
-          if constexpr (POS && FAST && FULL) {
+          if constexpr (F::POS && F::FAST && FULL) {
             // the stored f16 values directly (see pendh)
             h4 hv = to_h4<false>(acc[mt]);
             if (inv_is_h) {
@@ -2167,21 +2161,21 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
             continue;
           }
           f4 v = acc[mt] * inv_s;
-          if constexpr (REF) {
+          if constexpr (F::REF) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = r16(r16(acc[mt][i]) * inv_s);
           }
-          if constexpr (RMASK && !(FAST && FULL)) keep[kt][mt] = (full || row < a.M) ? v : z4;
+          if constexpr (F::RMASK && !(F::FAST && FULL)) keep[kt][mt] = (full || row < a.M) ? v : z4;
           if (full || row < a.M) {
-            if constexpr (FAST && FULL)
+            if constexpr (F::FAST && FULL)
               pend[kt][mt] = v;
             else
               put(row, kt, v);
           }
         }
       }
-      if constexpr (FAST && FULL) pend_tile = tile;
-      if constexpr (RMASK && !(FAST && FULL)) {
+      if constexpr (F::FAST && FULL) pend_tile = tile;
+      if constexpr (F::RMASK && !(F::FAST && FULL)) {
         bool nz[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) nz[mt] = nz_of(keep[0][mt], keep[1][mt]);
@@ -2190,16 +2184,9 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
     }
     // the last dW MFMAs of the tile have written their accumulators before anything
     // (a loop-exit copy) reads them
-    agpr_fence();
-    if constexpr (!POS) {
-      agpr_pin(dD2);
-      agpr_pin(dD1);
-      agpr_pin(dD0);
-      agpr_pin(dP1);
-    }
-    agpr_pin(dP0);
+    fence();
   };
-  if constexpr (REF == 3) {
+  if constexpr (F::LIST) {
     // the listed tiles, strided over the grid's wavefronts (the general per-tile path: a
     // listed tile's neighbours are not this wave's)
     const int64_t nw = static_cast<int64_t>(gridDim.x) * waves;
@@ -2217,7 +2204,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
         process(full_tile, tile + 1, nr1, nr0);
       }
       if (tile < t_full_end) process(full_tile, tile, nr0, nr1);
-      if constexpr (FAST) {
+      if constexpr (F::FAST) {
         if (t_begin < t_full_end) store_pend();
       }
     }
@@ -2225,15 +2212,8 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       process(std::integral_constant<bool, false>{}, tile, nr0, nr1);
   }
 
-  agpr_fence();
-  if constexpr (!POS) {
-    agpr_pin(dD2);
-    agpr_pin(dD1);
-    agpr_pin(dD0);
-    agpr_pin(dP1);
-  }
-  agpr_pin(dP0);
-  // dW flush: each wavefront's partials (unscaled by its own gradient scale) go into the
+  fence();
+  // ---- 8, dW flush: each wavefront's partials (unscaled by its own gradient scale) go into the
   // block's LDS sums, then the block adds them to the f32 gradients with one coalesced
   // atomic per parameter: a quarter of the r03 memory-side requests (one set per
   // wavefront; ~33 us per launch at 1,024 wavefronts, fixed in M)
@@ -2246,7 +2226,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   };
 #pragma unroll
   for (int kt = 0; kt < NT; ++kt) {
-    if constexpr (!POS) {
+    if constexpr (!F::POS) {
       flush(rdir + N::D2, W, dD2[kt], 0, 16 * kt + li);
       flush(rpos + N::P1, W, dP1[kt], 0, 16 * kt + li);
     } else {
@@ -2261,7 +2241,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
       }
     }
   }
-  if constexpr (NHD == 2 && !POS) {
+  if constexpr (NHD == 2 && !F::POS) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -2271,7 +2251,7 @@ __global__ void __launch_bounds__(256) bwd_rt_kernel(Args a, float target, int64
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
-      if constexpr (!POS) {
+      if constexpr (!F::POS) {
         if constexpr (S == 1) {
           flush(rdir + N::D0, 32, dD0[nt * 2 + kt], 16 * nt, dir_col<1>(16 * kt + li));
         } else {
@@ -2407,12 +2387,18 @@ static BwdGeom tile_geom(int64_t M, BwdKernel fn) {
   const int64_t nw = blocks * kBlockWaves;
   return {blocks, nw, (tiles + nw - 1) / nw};
 }
-// every backward form of one d_color layout (fast or general) runs the grid of its plain
-// (REF 0, f32-gradient) instantiation
+// the kernel of form Fast or General, by the d_color layout
+template <int W, int NHD, bool BF, int S, typename Fast, typename General>
+static BwdKernel bwd_kernel(bool fast) {
+  static_assert(Fast::FAST && !General::FAST, "the two d_color layouts of one form");
+  return fast ? bwd_rt_kernel<W, NHD, BF, S, Fast> : bwd_rt_kernel<W, NHD, BF, S, General>;
+}
+// every whole-network form of one d_color layout (fast or general) runs the grid of its
+// Build, dense-rows instantiation
 template <int W, int NHD, bool BF, int S>
 static BwdGeom bwd_geom(int64_t M, bool fast) {
-  return tile_geom(M, fast ? bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>
-                           : bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>);
+  return tile_geom(M, bwd_kernel<W, NHD, BF, S, Build<FastColor, DenseRows>,
+                                 Build<GeneralColor, DenseRows>>(fast));
 }
 
 template <int W, int NHD, bool BF, int S>
@@ -2434,16 +2420,15 @@ static void launch_bwd(BwdKernel k, int64_t blocks, const Args& a, float target,
                      tpw, wmax);
 }
 
-// reference numerics (the register-transposed kernel, REF), f16 (HG) or f32 incoming gradients
-template <int W, int NHD, bool HG>
+// reference numerics, f16 (Grads = F16Grads) or f32 incoming gradients
+template <int W, int NHD, typename Grads>
 static Plan plan_bwd_ref(const Args& a, bool fast, hipStream_t st) {
   if (a.d_enc_h && fast && a.tile_list) {
-    // the pos pass (REF 4) over every tile, on a grid of its own occupancy (more waves per
-    // SIMD: no dir network's registers or LDS sums in it), then the list pass (REF 3) over
-    // the tiles it left (nonzero dL/dcolor), at most one per wavefront of a grid of its
-    // occupancy
-    const BwdKernel pos = bwd_rt_kernel<W, NHD, true, false, false, 4, HG>;
-    const BwdKernel list = bwd_rt_kernel<W, NHD, true, false, false, 3, HG>;
+    // the pos pass over every tile, on a grid of its own occupancy (more waves per SIMD: no
+    // dir network's registers or LDS sums in it), then the list pass over the tiles it left
+    // (nonzero dL/dcolor), at most one per wavefront of a grid of its occupancy
+    const BwdKernel pos = bwd_rt_kernel<W, NHD, false, 1, PosPass<Grads>>;
+    const BwdKernel list = bwd_rt_kernel<W, NHD, false, 1, ListPass<Grads>>;
     const BwdGeom pg = tile_geom(a.M, pos);
     if (hipMemsetAsync(a.tile_count, 0, sizeof(uint32_t), st) != hipSuccess)
       return Plan::no_kernel;
@@ -2454,11 +2439,10 @@ static Plan plan_bwd_ref(const Args& a, bool fast, hipStream_t st) {
   }
   BwdKernel k = nullptr;
   if (a.d_enc_h)  // f16 rows and row bits
-    k = fast ? bwd_rt_kernel<W, NHD, true, false, false, 2, HG>
-             : bwd_rt_kernel<W, NHD, false, false, false, 2, HG>;
-  else if constexpr (!HG)  // f32 rows
-    k = fast ? bwd_rt_kernel<W, NHD, true, false, false, 1>
-             : bwd_rt_kernel<W, NHD, false, false, false, 1>;
+    k = bwd_kernel<W, NHD, false, 1, RefF16Rows<FastColor, Grads>,
+                   RefF16Rows<GeneralColor, Grads>>(fast);
+  else if constexpr (!Grads::value)  // f32 rows
+    k = bwd_kernel<W, NHD, false, 1, RefF32Rows<FastColor>, RefF32Rows<GeneralColor>>(fast);
   if (!k) return Plan::no_kernel;  // f16 gradients come with f16 rows only
   const BwdGeom gm = bwd_geom<W, NHD, false, 1>(a.M, fast);
   launch_bwd(k, gm.blocks, a, 0.0f, gm.tpw, nullptr, st);
@@ -2478,7 +2462,8 @@ static Plan plan_bwd(const Args& a, float* ws, int64_t ws_bytes, hipStream_t st)
       return Plan::no_kernel;
     } else {
       if (a.rows) return Plan::no_kernel;
-      return hg ? plan_bwd_ref<W, NHD, true>(a, fast, st) : plan_bwd_ref<W, NHD, false>(a, fast, st);
+      return hg ? plan_bwd_ref<W, NHD, F16Grads>(a, fast, st)
+                : plan_bwd_ref<W, NHD, F32Grads>(a, fast, st);
     }
   }
   // build numerics: the wavefronts' gradient maxima (f16 only), then the fast or general kernel
@@ -2488,12 +2473,13 @@ static Plan plan_bwd(const Args& a, float* ws, int64_t ws_bytes, hipStream_t st)
   if (!BF && (ws == nullptr || ws_bytes < static_cast<int64_t>(sizeof(float)) * gm.nw))
     return Plan::workspace;
   void (*amax)(Args, int64_t, float*) = absmax_kernel<false, S>;
-  BwdKernel k = fast ? bwd_rt_kernel<W, NHD, true, false, BF, 0, false, S>
-                     : bwd_rt_kernel<W, NHD, false, false, BF, 0, false, S>;
+  BwdKernel k = bwd_kernel<W, NHD, BF, S, Build<FastColor, DenseRows>,
+                           Build<GeneralColor, DenseRows>>(fast);
   if constexpr (S == 1) {
     if (a.rows) {
       amax = absmax_kernel<true>;
-      k = fast ? bwd_rt_kernel<W, NHD, true, true, BF> : bwd_rt_kernel<W, NHD, false, true, BF>;
+      k = bwd_kernel<W, NHD, BF, 1, Build<FastColor, GatheredRows>,
+                     Build<GeneralColor, GatheredRows>>(fast);
     }
   }
   if (!BF) hipLaunchKernelGGL(amax, dim3(gm.nw), dim3(1024), 0, st, a, gm.tpw * 32, ws);

@@ -1,11 +1,11 @@
-"""The pos pass of the reference-numerics field backward (bwd_rt_kernel<..., REF = 4>,
+"""The pos pass of the reference-numerics field backward (bwd_rt_kernel<..., PosPass<Grads>>,
 csrc/field_fused.hip) with its rank-1 output layer: dL/dpos_out of a zero-colour tile is
 dL/dsigma in unit 0 and zeros elsewhere, so dL/dhidden is one f16 product per value
 (P1[0][u] * dpo0) and only row 0 of dW_P1 is summed, both on the vector ALU instead of
 MFMAs against 15 zero columns.
 
 Each workspace form (``rows_ws``, ``rows_h_ws``: pos pass + list pass) runs against the
-single-kernel form (``rows``, REF 2, which keeps the MFMA arithmetic) and against
+single-kernel form (``rows``, RefF16Rows, which keeps the MFMA arithmetic) and against
 oracle/ref_ingp.field_reference (f64 arm):
 
 * dL/denc, the row bits and the listed-tile count are exact (torch.equal / the count of

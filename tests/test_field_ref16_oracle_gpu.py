@@ -1,5 +1,5 @@
-"""Every reference-numerics entry form of the fused field backward (bwd_rt_kernel<..., REF,
-HG>, csrc/field_fused.hip) against the oracle's field chain in reference semantics
+"""Every reference-numerics entry form of the fused field backward (bwd_rt_kernel<..., F>,
+the forms F with reference numerics, csrc/field_fused.hip) against the oracle's field chain in reference semantics
 (oracle/ref_ingp.field_reference, f64 arm), on inputs where the dir network's backward does
 nonzero work: live f16 dL/dcolor, about half of it subnormal once loss-scaled, mixed with
 zero-colour tiles (pos pass), gradient-free tiles (skipped) and a ray with dL/dsigma alone

@@ -55,12 +55,13 @@ TAGS = {  # prefixes: one instantiation of each per bench run (width / dtype fol
     "field_fwd": ("field::fwd_kernel<", ", true>(anr::field::Args)"),
     "field_fwd_f32io": ("field::fwd_kernel<", ", false>(anr::field::Args)"),
     # reference numerics: the pos pass (zero-colour tiles) and the list pass (r06), reading
-    # f16 gradients (last argument true; false with ANR_REF_F16_IO=0: the _f32io tags)
-    "field_bwd": "field::bwd_rt_kernel<64, 2, true, false, false, 4, true>",
-    "field_bwd_list": "field::bwd_rt_kernel<64, 2, true, false, false, 3, true>",
-    "field_bwd_f32io": "field::bwd_rt_kernel<64, 2, true, false, false, 4, false>",
-    "field_bwd_list_f32io": "field::bwd_rt_kernel<64, 2, true, false, false, 3, false>",
-    "field_bwd_build": "field::bwd_rt_kernel<64, 2, true, false, false, 0, false>",
+    # f16 gradients (F16Grads; F32Grads with ANR_REF_F16_IO=0: the _f32io tags). Names:
+    # bwd_rt_kernel<W, NHD, BF, S, form>, the forms of csrc/field_fused.hip
+    "field_bwd": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::PosPass<anr::field::F16Grads>",
+    "field_bwd_list": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::ListPass<anr::field::F16Grads>",
+    "field_bwd_f32io": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::PosPass<anr::field::F32Grads>",
+    "field_bwd_list_f32io": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::ListPass<anr::field::F32Grads>",
+    "field_bwd_build": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::Build<anr::field::FastColor, anr::field::DenseRows>",
     "field_bwd_lds": "field::bwd_kernel<",
     "composite_fwd": "rb::fwd_kernel<float, 4, 1, 4>",
     "composite_bwd": "rb::bwd_kernel<float, 4, 1, 4>",

@@ -334,7 +334,9 @@ __device__ __forceinline__ void deltas(const float* zrow, float zscale, int i0, 
   for (int j = 0; j < SPL; ++j) zs[j] = j < nvalid ? zr[j] * zscale : 0.0f;
   float prev = shfl_up(zs[SPL - 1], 1);  // last sample of lane-1
   float next = shfl_down(zs[0], 1);      // first sample of lane+1
-  if (lane == 0 && i0 > 0) prev = zrow[i0 - 1] * zscale;
+  // nvalid > 0: a wave that lies wholly past the ray's end (N = 257: waves 2 and 3 of
+  // SPL = 2) must not read z behind the row, which for the last ray is behind the tensor
+  if (lane == 0 && i0 > 0 && nvalid > 0) prev = zrow[i0 - 1] * zscale;
   if (lane == 63 && i0 + SPL < N) next = zrow[i0 + SPL] * zscale;
 #pragma unroll
   for (int j = 0; j < SPL; ++j) {
@@ -707,7 +709,17 @@ static bool launch_rb(bool bwd, const CompArgs& a, hipStream_t st) {
     case 3: ANR_RB_S(3, 4)
     case 4: ANR_RB_S(4, 4)
     case 8: ANR_RB_S(8, 4)
-    case 16: ANR_RB_S(16, 4)
+    case 16:
+      // The backward with 64 values per lane (SPL = 16, S = 4) does not fit 512 VGPRs: built
+      // that way it spills VGPRs to scratch and SGPRs to VGPR lanes and returned wrong
+      // dL/dsigma (1e5 error bounds off at N = 3841 and 4096, thin air, every other form and
+      // its own forward exact). It is not instantiated; the shape goes to the generic
+      // backward, which refuses what does not fit its LDS.
+      if (bwd && a.S == 4) return false;
+      if (a.S == 1) ANR_RB(16, 1, 4);
+      else if (!bwd) hipLaunchKernelGGL((rb::fwd_kernel<T, 16, 4, 4>),
+                                        dim3(static_cast<unsigned>(a.B)), dim3(256), 0, st, a);
+      return true;
     default: return false;
   }
 #undef ANR_RB_S

@@ -770,7 +770,9 @@ int anr_composite_force_generic(int32_t on);
 /* Backward. Gradients in (nullable; io_dtype): d_color_map, d_atmo, d_surf (B,C),
  * d_weights (B,N,S), d_alpha (B,N,S). Outputs (nullable): d_color (B,N,C),
  * d_sigma (B,N,S), d_color_surf (B,C) (io_dtype), d_z (B,N) f32 (dL/dz before scaling
- * by z_scale is applied, i.e. w.r.t. the unscaled z input). */
+ * by z_scale is applied, i.e. w.r.t. the unscaled z input). Shapes outside the
+ * register-blocked kernels, and S = 4 with N > 3840, run the generic backward, which stages
+ * (2S+1)*N floats per ray in LDS and returns ANR_E_INVALID ("too large") above 64 KiB. */
 int anr_composite_bwd(const float* z, float z_scale, const void* color, const void* sigma,
                       const void* color_surf, int32_t io_dtype, int64_t B, int32_t N,
                       int32_t C, int32_t S, const void* d_color_map, const void* d_atmo,

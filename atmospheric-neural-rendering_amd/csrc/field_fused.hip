@@ -921,7 +921,7 @@ struct HashArgs {
   uint32_t out_bytes;    // bytes of the plane buffer (range check of the stores)
 };
 
-template <int W, int NHD, bool BF, int WAVES, int OCC, int DEDUP>
+template <int W, int NHD, bool BF, int WAVES, int OCC>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)))
 hf_fwd_kernel(Args a, HashArgs h) {
   using N = Net<W, NHD>;
@@ -946,13 +946,13 @@ hf_fwd_kernel(Args a, HashArgs h) {
     const uint32_t m = static_cast<uint32_t>(st * 64) + lane;
     // ---- hash phase: lane = sample (coordinates past x's end read as 0, stores past M
     // dropped by the range check)
-    const auto xr = __builtin_amdgcn_raw_buffer_load_b96(rx, m * 12u, 0, 0);
-    const float xv[3] = {__uint_as_float(xr[0]), __uint_as_float(xr[1]), __uint_as_float(xr[2])};
+    float xv[3];
+    load_row<3>(rx, m * 12u, xv);
     const uint32_t orow = m < a.M ? m * 16u : 0x80000000u;
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
       uint32_t p[4];
-      plane_quad<3, __half, DEDUP>(h.G, 16, q, xv, rt, p);
+      plane_quad<3, __half, false>(h.G, 16, q, xv, rt, p);
       const u4q v = {p[0], p[1], p[2], p[3]};
       __builtin_amdgcn_raw_buffer_store_b128(v, ro, static_cast<uint32_t>(q) * h.plane_bytes + orow,
                                              0, 0);
@@ -1147,7 +1147,7 @@ __device__ __forceinline__ void render_end_build(const RenderArgs& r, const Buil
   }
 }
 
-template <int W, int NHD, bool BF, bool REF, int WAVES, int OCC, int DEDUP>
+template <int W, int NHD, bool BF, bool REF, int WAVES, int OCC>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(OCC)))
 render_kernel(Args a, HashArgs h, RenderArgs r) {
   using N = Net<W, NHD>;
@@ -1190,12 +1190,12 @@ render_kernel(Args a, HashArgs h, RenderArgs r) {
       const float zp = i < n - 1 ? zr[i + 1] : 0.0f;
       // ---- hash phase: lane = sample (every sample of the ray is in range)
       const uint32_t m = static_cast<uint32_t>(b * n + i);
-      const auto xr = __builtin_amdgcn_raw_buffer_load_b96(rx, m * 12u, 0, 0);
-      const float xv[3] = {__uint_as_float(xr[0]), __uint_as_float(xr[1]), __uint_as_float(xr[2])};
+      float xv[3];
+      load_row<3>(rx, m * 12u, xv);
 #pragma unroll 1
       for (int q = 0; q < 4; ++q) {
         uint32_t p[4];
-        plane_quad<3, __half, DEDUP>(h.G, 16, q, xv, rt, p);
+        plane_quad<3, __half, false>(h.G, 16, q, xv, rt, p);
         stage[wave][q][lane] = u4q{p[0], p[1], p[2], p[3]};
       }
       ::anr::ref16::wave_sync();
@@ -2511,12 +2511,12 @@ static int variant(const anr_mlp_desc* pos, const anr_mlp_desc* dir) {
 // as the device holds at once, each wavefront walking 64-sample segments grid-stride
 constexpr int HF_WAVES = 8;
 // register cap of the fused forward: 6 waves per SIMD. It runs without run-leader gathers
-// (DEDUP 0): with them it measured 0.74-0.79 ms at caps of 4, 5 and 6 against 0.64-0.65 ms
+// (plane_quad's LEADERS off): with them it measured 0.74-0.79 ms at caps of 4, 5 and 6 against 0.64-0.65 ms
 // without (profiles/r06_hash_field_fwd_variants.log).
 constexpr int HF_OCC = 6;
 template <int W, int NHD, bool BF>
 static Plan plan_hf(const Args& a, const HashArgs& h, hipStream_t st) {
-  const auto k = hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC, 0>;
+  const auto k = hf_fwd_kernel<W, NHD, BF, HF_WAVES, HF_OCC>;
   const int64_t n_super = (a.M + 63) / 64;
   const int64_t blocks =
       persistent_blocks((n_super + HF_WAVES - 1) / HF_WAVES,
@@ -2531,7 +2531,7 @@ constexpr int RN_WAVES = 8;
 constexpr int RN_OCC = 4;
 template <int W, int NHD, bool BF, bool REF>
 static Plan plan_render(const Args& a, const HashArgs& h, const RenderArgs& r, hipStream_t st) {
-  const auto k = render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC, 0>;
+  const auto k = render_kernel<W, NHD, BF, REF, RN_WAVES, RN_OCC>;
   const int64_t blocks =
       persistent_blocks((r.B + RN_WAVES - 1) / RN_WAVES,
                         resident_blocks(reinterpret_cast<const void*>(k), 64 * RN_WAVES));

@@ -5,16 +5,6 @@
 
 #include "anr_common.h"
 
-#ifndef HASH_DEDUP
-// plane_quad: levels whose cells change at no more than this many of a wavefront's lanes
-// gather at the run leaders only (see there); 0 = every lane gathers, 64 = every level
-#define HASH_DEDUP 64
-#endif
-#ifndef HASH_FMA_MIX
-// Raw2<__half>::fma2 as v_fma_mix_f32 (1) or f16 -> f32 conversions + f32 FMAs (0)
-#define HASH_FMA_MIX 1
-#endif
-
 namespace anr {
 
 struct GridLevels {
@@ -85,7 +75,21 @@ struct LevelIdx {
       comp[d][1] = comp[d][0] + mul[d];
     }
   }
-  // corner c: bit d = offset along dimension d
+  // The dense wrap of a corner sum >= T: one subtraction, the division only past 2 T
+  __device__ uint32_t wrap(uint32_t sum) const {
+    const uint32_t s1 = sum - T;
+    return s1 < T ? s1 : sum % T;
+  }
+  // The far-face test, once per cell: a dense corner sum can reach T only with a corner on
+  // the far face or outside the grid (below that every sum is <= res^D - 1 < T); the
+  // unsigned maximum also catches negative cell coordinates.
+  __device__ bool far_face(const uint32_t* g) const {
+    uint32_t gmax = g[0];
+#pragma unroll
+    for (int d = 1; d < D; ++d) gmax = gmax > g[d] ? gmax : g[d];
+    return gmax >= res1;
+  }
+  // corner c: bit d = offset along dimension d (the v1 forward: a branch per corner)
   __device__ uint32_t corner(const uint32_t (*comp)[2], int c) const {
     uint32_t hx = 0u, sum = 0u;
 #pragma unroll
@@ -94,11 +98,56 @@ struct LevelIdx {
       sum += comp[d][(c >> d) & 1];
     }
     if (hashed) return hx & (T - 1u);
-    if (sum < T) return sum;
-    const uint32_t s1 = sum - T;
-    return s1 < T ? s1 : sum % T;
+    return sum < T ? sum : wrap(sum);
+  }
+  // All 2^D corners of cell g at once, branch-free apart from the wrap: corner c's bit d
+  // picks comp[d][.]; the hashed / dense choice is a select on the level's flag, the wrap one
+  // rarely-taken branch per cell behind the far-face test. A branch-free wrap (selects on
+  // every cell, the modulo behind one wave-uniform test) measured slower: hash bwd 0.39-0.41
+  // -> 0.45-0.47 ms (profiles/r06_hash_dense_wrap_ab.log)
+  __device__ void corners(const uint32_t (*comp)[2], const uint32_t* g, uint32_t* idx) const {
+    uint32_t sum[1 << D];
+#pragma unroll
+    for (int c = 0; c < (1 << D); ++c) {
+      uint32_t hx = 0u, sm = 0u;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        hx ^= comp[d][(c >> d) & 1];
+        sm += comp[d][(c >> d) & 1];
+      }
+      sum[c] = sm;
+      idx[c] = hashed ? (hx & (T - 1u)) : sm;
+    }
+    if (!hashed && far_face(g)) {
+#pragma unroll
+      for (int c = 0; c < (1 << D); ++c)
+        if (sum[c] >= T) idx[c] = wrap(sum[c]);
+    }
   }
 };
+
+// The cell split of tcnn's linear interpolation: lattice cell g and weights w of the sample
+// at xv on a level of scale `scale`
+template <int D>
+__device__ __forceinline__ void cell_split(float scale, const float* xv, uint32_t* g, float* w) {
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    const float p = fmaf(scale, xv[d], 0.5f);
+    const float fl = floorf(p);
+    g[d] = static_cast<uint32_t>(static_cast<int>(fl));
+    w[d] = p - fl;
+  }
+}
+
+// Weight of corner c (bit d = offset along dimension d): the product over the dimensions,
+// in dimension order
+template <int D>
+__device__ __forceinline__ float corner_weight(const float* w, int c) {
+  float wt = 1.0f;
+#pragma unroll
+  for (int d = 0; d < D; ++d) wt *= ((c >> d) & 1) ? w[d] : 1.0f - w[d];
+  return wt;
+}
 
 template <typename TT>
 struct Raw2;
@@ -122,14 +171,8 @@ struct Raw2<__half> {
   // plus an f32 FMA (hipcc emits the two: it forms v_fma_mix only when f32 denormals are
   // flushed; these products are far above the f32 denormal range)
   __device__ static void fma2(float wt, type v, float& a0, float& a1) {
-#if HASH_FMA_MIX
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel_hi:[0,1,0]" : "+v"(a0) : "v"(wt), "v"(v));
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(a1) : "v"(wt), "v"(v));
-#else
-    const __half2 h = __builtin_bit_cast(__half2, v);
-    a0 = fmaf(wt, __low2float(h), a0);
-    a1 = fmaf(wt, __high2float(h), a1);
-#endif
   }
 };
 template <>
@@ -161,12 +204,33 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const void* p, uint3
                                            0x00020000);
 }
 
+// One row of D coordinates at byte offset off of the descriptor rx (past the end: zeros)
+template <int D>
+__device__ __forceinline__ void load_row(__amdgpu_buffer_rsrc_t rx, uint32_t off, float* xv) {
+  static_assert(D >= 2 && D <= 4, "coordinate rows of 2 to 4 floats");
+  if constexpr (D == 4) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) xv[d] = __uint_as_float(v[d]);
+  } else if constexpr (D == 3) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b96(rx, off, 0, 0);
+    xv[0] = __uint_as_float(v[0]);
+    xv[1] = __uint_as_float(v[1]);
+    xv[2] = __uint_as_float(v[2]);
+  } else {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rx, off, 0, 0);
+    xv[0] = __uint_as_float(v[0]);
+    xv[1] = __uint_as_float(v[1]);
+  }
+}
 
 // Level quad q (levels 4q..4q+3, 2 features each, f16 pairs packed in four u32; a partial
 // last quad is zero-filled) of the sample at coordinates xv: the forward v9 arithmetic
 // (one lane per sample, every corner gathered through the table descriptor rt; same corner
 // order, weights and fma chain as the walkers, bit-identical to them).
-template <int D, typename TT, int DEDUP = HASH_DEDUP>
+// LEADERS: gather at the run leaders only (below). anr_hashgrid_fwd_planes runs with them;
+// the fused hash + field forward and the render kernel without (field_fused.hip, plan_hf).
+template <int D, typename TT, bool LEADERS>
 __device__ __forceinline__ void plane_quad(const GridLevels& G, int n_levels, int q,
                                            const float* xv, __amdgpu_buffer_rsrc_t rt,
                                            uint32_t (&packed)[4]) {
@@ -185,13 +249,7 @@ __device__ __forceinline__ void plane_quad(const GridLevels& G, int n_levels, in
     const uint32_t hmask = T - 1u;
     float w[D];
     uint32_t g[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const float p = fmaf(scale, xv[d], 0.5f);
-      const float fl = floorf(p);
-      g[d] = static_cast<uint32_t>(static_cast<int>(fl));
-      w[d] = p - fl;
-    }
+    cell_split<D>(scale, xv, g, w);
     // idx: the corners' byte offsets within the level (its base goes to the loads' SGPR
     // offset). Hashed levels (wave-uniform branch) hash byte-scaled components: R::bytes is
     // a power of two, so (a*k ^ b*k ^ c*k) & (T-1)*k == ((a ^ b ^ c) & (T-1)) * k, bits
@@ -216,39 +274,21 @@ __device__ __forceinline__ void plane_quad(const GridLevels& G, int n_levels, in
     } else {
       uint32_t comp[D][2];
       li.dims(g, comp);
-      uint32_t sum[1 << D];
-#pragma unroll
-      for (int c = 0; c < (1 << D); ++c) {
-        uint32_t sm = 0u;
-#pragma unroll
-        for (int d = 0; d < D; ++d) sm += comp[d][(c >> d) & 1];
-        sum[c] = sm;
-        idx[c] = sm;
-      }
-      uint32_t gmax = g[0];
-#pragma unroll
-      for (int d = 1; d < D; ++d) gmax = gmax > g[d] ? gmax : g[d];
-      if (gmax >= res - 1u) {
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c)
-          if (sum[c] >= T) {
-            const uint32_t s1 = sum[c] - T;
-            idx[c] = s1 < T ? s1 : sum[c] % T;
-          }
-      }
+      li.corners(comp, g, idx);
 #pragma unroll
       for (int c = 0; c < (1 << D); ++c) idx[c] *= R::bytes;
     }
     typename R::type val[1 << D];
-    bool plain = true;
-    if constexpr (DEDUP > 0) {
+    if constexpr (LEADERS) {
       // Lanes are consecutive samples of a ray, so runs of lanes share a cell (one run per
       // wavefront on the coarse levels, every few samples on the finest). The gathers'
       // cost is address processing per active lane (profiles/r06_ta_probe.log: masked
       // lanes are skipped), so only the first lane of each run gathers and the run's other
       // lanes take its corner values through ds_bpermute (the LDS crossbar, not the
-      // texture path). Levels whose cells change at more than DEDUP lanes gather
-      // plainly. The same entries reach every lane: bit-identical.
+      // texture path). The same entries reach every lane: bit-identical. Every level does
+      // so, however many runs it has: on the settled bench step, hash fwd 0.478 ms with plain
+      // gathers, 0.435 / 0.439 / 0.433 / 0.421 ms with run leaders on the levels of at most
+      // 32 / 16 / 48 / 64 runs per wavefront (profiles/r06_hash_fwd_dedup_sweep.log)
       const int lane = __lane_id();
       bool lead = lane == 0;
 #pragma unroll
@@ -259,31 +299,22 @@ __device__ __forceinline__ void plane_quad(const GridLevels& G, int n_levels, in
         lead = lead || pg != g[d];
       }
       const uint64_t lm = __ballot(lead);
-      if (__popcll(lm) <= DEDUP) {  // wave-uniform
-        plain = false;
-        // this lane's run leader: the highest leading lane at or below it
-        const uint64_t below = lm & ((2ull << lane) - 1ull);
-        const int src = 63 - static_cast<int>(__clzll(static_cast<long long>(below)));
-        if (lead) {
+      // this lane's run leader: the highest leading lane at or below it
+      const uint64_t below = lm & ((2ull << lane) - 1ull);
+      const int src = 63 - static_cast<int>(__clzll(static_cast<long long>(below)));
+      if (lead) {
 #pragma unroll
-          for (int c = 0; c < (1 << D); ++c) val[c] = R::load(rt, idx[c], base);
-        }
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c) val[c] = R::from_lane(val[c], src);
+        for (int c = 0; c < (1 << D); ++c) val[c] = R::load(rt, idx[c], base);
       }
-    }
-    if (plain) {
+#pragma unroll
+      for (int c = 0; c < (1 << D); ++c) val[c] = R::from_lane(val[c], src);
+    } else {
 #pragma unroll
       for (int c = 0; c < (1 << D); ++c) val[c] = R::load(rt, idx[c], base);
     }
     float a0 = 0.0f, a1 = 0.0f;
 #pragma unroll
-    for (int c = 0; c < (1 << D); ++c) {
-      float wt = 1.0f;
-#pragma unroll
-      for (int d = 0; d < D; ++d) wt *= ((c >> d) & 1) ? w[d] : 1.0f - w[d];
-      R::fma2(wt, val[c], a0, a1);
-    }
+    for (int c = 0; c < (1 << D); ++c) R::fma2(corner_weight<D>(w, c), val[c], a0, a1);
     packed[j] = __builtin_bit_cast(uint32_t, __floats2half2_rn(a0, a1));
   }
 }

@@ -10,40 +10,56 @@
 //   index   = dense stride index while stride <= T_l, else XOR prime hash; % T_l
 //   out[l*F + f] = sum over 2^D corners of prod(w or 1-w) * table[(off_l + index)*F + f]
 //
-// Work decomposition (MI355X-specific): one thread owns one LEVEL of a CHUNK of K
-// consecutive samples. Samples are ray-major, so consecutive samples of a ray usually
-// stay in the same cell of a level (always on the coarse levels, ~4 samples per cell on
-// the finest). The forward keeps the 2^D corner features of the current cell in
-// registers and re-gathers only when the cell changes; the backward accumulates the
-// corner gradients of the current cell in registers and issues the f32 atomics only
-// when the cell changes. Lanes of a wavefront are the levels of one chunk (16 levels ->
-// 4 chunks per wave): the per-sample coordinate load is a broadcast and the per-sample
-// feature row (L*F values) is read/written contiguously.
+// The per-sample arithmetic (cell split, corner weight, corner indices with the dense wrap,
+// coordinate row load) is stated once, in hash_levels.h, and used wherever it leaves the
+// machine code in place (DESIGN.md §5 K3/K4 "Forms": the generic v1 kernels spell some of it
+// out); grid_index there is the plain definition the others are tested against.
+//
+// Samples are ray-major, so consecutive samples of a ray usually stay in the same cell of a
+// level (always on the coarse levels, ~4 samples per cell on the finest). The walkers (v1,
+// v6, v2) put a lane on one level of a CHUNK of K consecutive samples and touch the table
+// only when the cell changes; the planes forward (v9) puts a lane on one sample. Which
+// kernel serves which entry point:
+//
+//   entry point                shape                                   kernel
+//   anr_hashgrid_fwd_planes    2 features, <= 16 levels, 2-D to 4-D    hashgrid_fwd_planes_kernel
+//     (training step, extract)
+//   anr_hashgrid_fwd, _runs    2 features, <= 16 levels, 2-D / 3-D,    hashgrid_fwd_v6_kernel
+//                              byte ranges below 2^31
+//                              every other grid (1/2/4/8 features,     hashgrid_fwd_kernel (v1)
+//                              4-D, > 16 levels), or mode 1 / 6
+//   anr_hashgrid_bwd           2 features, <= 16 levels, 2-D / 3-D,    hashgrid_bwd_v2_kernel
+//                              gradient table below 2 GB:
+//                                3-D, strides (3, 32)                    <DenseWalk<3, 32>>
+//                                other strides, 2-D, or mode 7           <DenseWalk<0, 0>>
+//                              every other grid, or mode 1             hashgrid_bwd_kernel (v1)
+//   anr_hashgrid_bwd_rows      the <3, 32> shape with 16 levels        <RowBitsWalk>
+//     (training step)          otherwise                               zero_clear_rows_kernel, then
+//                                                                      as anr_hashgrid_bwd
+//   anr_hashgrid_bwd_tiles     the <3, 32> shape, chunks of whole      <TileMaskWalk>
+//                              32-row tiles; otherwise                 as anr_hashgrid_bwd
+//   anr_hashgrid_bwd_count_requests   3-D v2 shape                     <CountRequests>
+//
+// (modes: anr_hashgrid_force_v1, the tests' hook; 0 is the default.) The fused hash + field
+// forward and the render kernel (field_fused.hip) run v9's plane_quad inside their own loops.
 
 #include "anr_common.h"
 #include "hash_levels.h"
 
-// Profiling ablation (tools): 1 = backward without its atomics. 0 in product builds.
-#ifndef HASH_BS
-// samples per prefetch batch of the v2 backward walker. 6 rather than 8: the batch's
-// scalar coordinates (two batches of 3 x BS SGPRs) spilled 40 SGPRs at 8, 3 at 6; on the
-// settled reference-numerics step's own inputs 0.717 -> 0.690 ms (with the max-ILP
-// scheduler 0.689; profiles/r05_hash_bwd_variants.log). The tile path keeps 8.
-#define HASH_BS 6
-#endif
-#ifndef HASH_FBS
-#define HASH_FBS 4  // samples per coordinate prefetch batch of the forward walker
-#endif
-#ifndef HASH_EXP
-#define HASH_EXP 0
-#endif
-
-
 #include <cmath>
+#include <initializer_list>
 #include <type_traits>
 #include <cstdlib>
 
 namespace anr {
+
+// Samples per prefetch batch of the v2 backward walker. 6 rather than 8: the batch's
+// scalar coordinates (two batches of 3 x BS SGPRs) spilled 40 SGPRs at 8, 3 at 6; on the
+// settled reference-numerics step's own inputs 0.717 -> 0.690 ms (with the max-ILP
+// scheduler 0.689; profiles/r05_hash_bwd_variants.log). The tile-mask walk keeps 8.
+constexpr int kBwdBatch = 6;
+// Samples per coordinate prefetch batch of the forward walkers
+constexpr int kFwdBatch = 4;
 
 // Corner addressing for the v2 walkers, where a lane owns the x-offset b and the NC =
 // 2^(D-1) corners over dims 1..D-1. The per-dimension components of the cell are formed
@@ -54,6 +70,8 @@ namespace anr {
 template <int D>
 struct LaneCorners {
   static constexpr int NC = 1 << (D - 1);
+  // lattice offset bit of corner c (0..NC-1) along dim d >= 1
+  __device__ static int bit(int c, int d) { return (c >> (d - 1)) & 1; }
   __device__ static void indices(const LevelIdx<D>& li, const uint32_t* cell, int b,
                                  uint32_t* idx) {
     const uint32_t cx = (cell[0] + static_cast<uint32_t>(b)) * li.mul[0];
@@ -131,7 +149,12 @@ struct LaneCorners {
 };
 
 template <typename T, int F>
-struct Vec;
+struct Vec {
+  __device__ static void load(const T* p, float* v) {
+#pragma unroll
+    for (int f = 0; f < F; ++f) v[f] = to_f32<T>(p[f]);
+  }
+};
 template <>
 struct Vec<__half, 2> {
   __device__ static void load(const __half* p, float* v) {
@@ -147,24 +170,6 @@ struct Vec<float, 2> {
     const float2 f = *reinterpret_cast<const float2*>(p);
     v[0] = f.x;
     v[1] = f.y;
-  }
-};
-template <typename T>
-struct Vec<T, 1> {
-  __device__ static void load(const T* p, float* v) { v[0] = to_f32<T>(p[0]); }
-};
-template <typename T>
-struct Vec<T, 4> {
-  __device__ static void load(const T* p, float* v) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) v[f] = to_f32<T>(p[f]);
-  }
-};
-template <typename T>
-struct Vec<T, 8> {
-  __device__ static void load(const T* p, float* v) {
-#pragma unroll
-    for (int f = 0; f < 8; ++f) v[f] = to_f32<T>(p[f]);
   }
 };
 
@@ -242,18 +247,17 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_kernel(
     for (int f = 0; f < F; ++f) acc[f] = 0.0f;
 #pragma unroll
     for (int c = 0; c < (1 << D); ++c) {
-      float wt = 1.0f;
+      float wt = 1.0f;  // corner_weight, spelled out: see DESIGN.md §5 K3/K4 "Forms"
 #pragma unroll
       for (int d = 0; d < D; ++d) wt *= ((c >> d) & 1) ? w[d] : 1.0f - w[d];
 #pragma unroll
       for (int f = 0; f < F; ++f) acc[f] = fmaf(wt, val[c][f], acc[f]);
     }
-    if constexpr ((HASH_EXP & 2) == 0) store_feat<TO, F>(out + m * out_stride + level * F, acc);
-    else if (acc[0] == 12345.0f) out[0] = from_f32<TO>(acc[F - 1]);  // keep the work alive
+    store_feat<TO, F>(out + m * out_stride + level * F, acc);
   };
 
   // coordinates prefetched one batch ahead (indices clamped to the chunk: no branch)
-  constexpr int BS = HASH_FBS;
+  constexpr int BS = kFwdBatch;
   float xb[BS][D], xn[BS][D];
   auto load_batch = [&](int64_t mb, float (*xo)[D]) {
 #pragma unroll
@@ -274,11 +278,6 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_kernel(
 #pragma unroll
       for (int d = 0; d < D; ++d) xb[j][d] = xn[j][d];
   }
-}
-
-template <typename TG>
-__device__ __forceinline__ float load_grad(const TG* p) {
-  return to_f32<TG>(*p);
 }
 
 template <int D, int F, typename TG>
@@ -332,15 +331,10 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(
   for (int64_t m = m0; m < m1; ++m) {
     float w[D];
     uint32_t g[D];
+    cell_split<D>(scale, x + m * x_stride, g, w);
     bool same = have;
 #pragma unroll
-    for (int d = 0; d < D; ++d) {
-      const float p = fmaf(scale, x[m * x_stride + d], 0.5f);
-      const float fl = floorf(p);
-      g[d] = static_cast<uint32_t>(static_cast<int>(fl));
-      w[d] = p - fl;
-      same = same & (g[d] == cell[d]);
-    }
+    for (int d = 0; d < D; ++d) same = same & (g[d] == cell[d]);
     if (!same) {
       if (have) flush();
       have = true;
@@ -349,10 +343,10 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(
     }
     float gv[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) gv[f] = load_grad<TG>(dout + m * dout_stride + level * F + f);
+    for (int f = 0; f < F; ++f) gv[f] = to_f32<TG>(dout[m * dout_stride + level * F + f]);
 #pragma unroll
     for (int c = 0; c < (1 << D); ++c) {
-      float wt = 1.0f;
+      float wt = 1.0f;  // corner_weight, spelled out: see DESIGN.md §5 K3/K4 "Forms"
 #pragma unroll
       for (int d = 0; d < D; ++d) wt *= ((c >> d) & 1) ? w[d] : 1.0f - w[d];
 #pragma unroll
@@ -362,22 +356,6 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_kernel(
   if (have) flush();
 }
 
-
-// ---------------------------------------------------------------------------------------
-// v2 (F = 2, L <= 16): 4 lanes per level, one chunk of K consecutive samples per wave.
-// lane = 4*level + 2*b + f owns feature f of the 2^(D-1) corners whose x-offset is b.
-// The 4 lanes of a level touch entries (x, x+1) x features (0, 1): adjacent addresses on
-// dense levels (and on hashed levels when x is even, since the first hash prime is 1),
-// so one wave instruction issues one memory request per level instead of four. When
-// the sample moves to a neighbouring cell with the same x, corners shared by the two
-// cells keep their accumulated gradient (bwd) / gathered feature (fwd).
-template <int D>
-struct Corners {
-  static constexpr int NC = 1 << (D - 1);
-  // lattice offset bit of corner c (0..NC-1) along dim d >= 1
-  __device__ static int bit(int c, int d) { return (c >> (d - 1)) & 1; }
-};
-
 // ---------------------------------------------------------------------------------------
 // Forward v6 (F = 2, L <= 16): v1's decomposition (lane = one level of one of the 4
 // chunks a wavefront walks side by side) with the per-sample instruction stream rebuilt.
@@ -385,10 +363,7 @@ struct Corners {
 // samples on the bench geometry), and its lanes mix dense and hashed levels, so in v1
 // every per-corner branch (hashed / dense / dense wrap) ran both ways on nearly every
 // sample, next to 64-bit clamped coordinate indices. Here:
-//   * corner indices are branch-free (hashed and dense forms, one select per corner); the
-//     dense wrap (a corner sum reaching T) is one rarely-taken branch per cell, entered
-//     only when a corner can reach the far face (cell coordinate >= res - 1 or outside the
-//     grid: below that every corner sum is <= res^D - 1 < T);
+//   * corner indices are branch-free apart from the dense wrap (LevelIdx::corners);
 //   * memory goes through buffer descriptors with 32-bit offsets: reads past the end of x
 //     return 0 and writes past the last row are dropped by the hardware range check, so
 //     the walk has no per-sample bounds checks and a wave-uniform trip count;
@@ -476,21 +451,8 @@ __device__ __forceinline__ void fwd_walk_v6(const GridLevels& G, int level, int6
             idx[c] = s1 < T ? s1 : sum[c] % T;
           }
       }
-      if constexpr ((HASH_EXP & 4) != 0 && std::is_same<TT, __half>::value) {
-        // ceiling probe (wrong values): one 8-B load per x-pair at the aligned pair of x0
 #pragma unroll
-        for (int c = 0; c < (1 << D); c += 2) {
-          const auto v = __builtin_amdgcn_raw_buffer_load_b64(rt, base + (idx[c] & ~1u) * 4u, 0, 0);
-          val[c] = v[0];
-          val[c + 1] = v[1];
-        }
-      } else if constexpr ((HASH_EXP & 8) != 0 && std::is_same<TT, __half>::value) {
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c) val[c] = idx[c];  // no gathers (probe, wrong values)
-      } else {
-#pragma unroll
-        for (int c = 0; c < (1 << D); ++c) val[c] = R::load(rt, base + idx[c] * R::bytes);
-      }
+      for (int c = 0; c < (1 << D); ++c) val[c] = R::load(rt, base + idx[c] * R::bytes);
 #pragma unroll
       for (int d = 0; d < D; ++d) cell[d] = g[d];
       have = true;
@@ -508,7 +470,7 @@ __device__ __forceinline__ void fwd_walk_v6(const GridLevels& G, int level, int6
   };
 
   // coordinates prefetched one batch ahead; past the end of x the loads return 0
-  constexpr int BS = HASH_FBS;
+  constexpr int BS = kFwdBatch;
   float xb[BS][D], xn[BS][D];
   auto load_batch = [&](float (*xo_)[D]) {
 #pragma unroll
@@ -571,7 +533,7 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_v6_kernel(
 // on the bench coordinates (profiles/r05_hash_fwd_planes.log): v6 0.634 ms, v9 0.47-0.50
 // ms; pinning level pairs to XCDs (block b -> XCD b % 8) made it slower (0.77 / 1.13 ms:
 // every XCD then reads every coordinate).
-template <int D, typename TT, int DEDUP>
+template <int D, typename TT>
 __global__ void __launch_bounds__(256) hashgrid_fwd_planes_kernel(
     GridLevels G, int n_levels, const float* __restrict__ x, uint32_t x_bytes, uint32_t xs4,
     int64_t M, const TT* __restrict__ table, uint32_t table_bytes, __half* __restrict__ out,
@@ -582,26 +544,13 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_planes_kernel(
   const __amdgpu_buffer_rsrc_t ro = wave_rsrc(out, out_bytes);
   const uint32_t xo = static_cast<uint32_t>(m) * xs4;  // past the end: loads return 0
   float xv[D];
-  if constexpr (D == 4) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rx, xo, 0, 0);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) xv[d] = __uint_as_float(v[d]);
-  } else if constexpr (D == 3) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b96(rx, xo, 0, 0);
-    xv[0] = __uint_as_float(v[0]);
-    xv[1] = __uint_as_float(v[1]);
-    xv[2] = __uint_as_float(v[2]);
-  } else {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rx, xo, 0, 0);
-    xv[0] = __uint_as_float(v[0]);
-    xv[1] = __uint_as_float(v[1]);
-  }
+  load_row<D>(rx, xo, xv);
   // rows past M: the stores are dropped by the range check (offset >= out_bytes)
   const uint32_t orow = m < M ? static_cast<uint32_t>(m) * 16u : 0x80000000u;
   const int n_quads = (n_levels + 3) >> 2;
   for (int q = 0; q < n_quads; ++q) {
     uint32_t packed[4];
-    plane_quad<D, TT, DEDUP>(G, n_levels, q, xv, rt, packed);
+    plane_quad<D, TT, true>(G, n_levels, q, xv, rt, packed);
     typedef uint32_t u4q __attribute__((vector_size(16)));
     const u4q v = {packed[0], packed[1], packed[2], packed[3]};
     __builtin_amdgcn_raw_buffer_store_b128(v, ro, static_cast<uint32_t>(q) * plane_bytes + orow,
@@ -609,11 +558,6 @@ __global__ void __launch_bounds__(256) hashgrid_fwd_planes_kernel(
   }
 }
 
-// XS / DS: compile-time coordinate and dL/dy row strides (0 = the run-time x_stride /
-// dout_stride). With both known (the fused field's (M,3) coordinates and (M,32) dL/denc)
-// every prefetch address is a per-batch scalar base plus immediate offsets: the walk
-// issues no per-sample address arithmetic (r01 spent ~25 scalar instructions per sample
-// on 64-bit clamped indices), and only a chunk's last two batches clamp.
 // Distinct 64-B segments among the active lanes' addresses: the memory-side requests one
 // wave-level float atomic instruction makes (MI355X_MICROARCH.md "Global float atomics").
 // Called in divergent code: the count is returned to the instruction's first active lane
@@ -634,20 +578,95 @@ __device__ __forceinline__ uint32_t distinct_segments(bool active, uint64_t seg)
   return first ? n : 0;
 }
 
-// COUNT: the request-count instrument (anr_hashgrid_bwd_count_requests): the same walk,
-// but every flush instruction adds its number of distinct 64-B segments to *count
-// instead of issuing the atomics (dtable is not written)
-// SPARSE: anr_hashgrid_bwd_rows: row_nz holds one bit per dL/dy row (32 rows per word,
-// written by anr_ingp_field_bwd_ref16_rows), and only the rows whose bit is set are loaded
-// and walked (16 levels: every lane takes part in the chunk's compaction)
-template <int D, typename TG, int XS, int DS, bool COUNT = false, int BSZ = HASH_BS,
-          bool SPARSE = false>
+// ---------------------------------------------------------------------------------------
+// The walks of the v2 backward: which rows of a chunk a wavefront loads and steps through.
+// A walk type states its batch size BS, its compile-time row strides XS / DS (0: the
+// run-time ones), what it needs beyond the common arguments (Args) and, in check<D>(), which
+// combinations exist.
+
+// Every row of the chunk in batches of BS, the next batch prefetched. With both strides
+// known (the fused field's (M,3) coordinates and (M,32) dL/denc) every prefetch address is a
+// per-batch scalar base plus immediate offsets: the walk issues no per-sample address
+// arithmetic (r01 spent ~25 scalar instructions per sample on 64-bit clamped indices), and
+// only a chunk's last two batches clamp. A batch, and inside a walked batch a sample, whose
+// dL/dy is zero in every lane is passed over (do_batch).
+template <int XS_, int DS_>
+struct DenseWalk {
+  static constexpr int XS = XS_, DS = DS_, BS = kBwdBatch;
+  static constexpr bool kCount = false;
+  struct Args {};
+  template <int D>
+  static constexpr void check() {
+    static_assert((XS == 0 && DS == 0) || (XS == 3 && DS == 32 && D == 3),
+                  "run-time strides, or the fused field's layout (3-D only)");
+  }
+};
+// anr_hashgrid_bwd_tiles: the field backward marked the 32-row tiles whose dL/dy is zero in
+// every row (it skipped them); their batches are neither loaded nor walked. The mask is laid
+// out for batches of 8: a 32-row tile is 4 of them.
+struct TileMaskWalk {
+  static constexpr int XS = 3, DS = 32, BS = 8;
+  static constexpr bool kCount = false;
+  struct Args {
+    const uint8_t* tile_nz;  // one flag per 32-row tile
+  };
+  template <int D>
+  static constexpr void check() {
+    static_assert(D == 3 && 32 % BS == 0, "fused-field layout; whole batches per tile");
+  }
+};
+// anr_hashgrid_bwd_rows: one bit per dL/dy row (32 rows per word, written by
+// anr_ingp_field_bwd_ref16_rows); only the rows whose bit is set are loaded and walked, after
+// an LDS compaction in which every lane of the wavefront takes part (so: 16 levels).
+struct RowBitsWalk {
+  static constexpr int XS = 3, DS = 32, BS = kBwdBatch;
+  static constexpr bool kCount = false;
+  struct Args {
+    const uint32_t* row_nz;
+  };
+  template <int D>
+  static constexpr void check() {
+    static_assert(D == 3, "fused-field layout");
+    static_assert(BS % 2 == 0, "row indices are read in pairs");
+  }
+};
+// The request-count instrument (anr_hashgrid_bwd_count_requests): the dense walk at run-time
+// strides, but every flush instruction adds its number of distinct 64-B segments to *count
+// instead of issuing the atomics (dtable is not written).
+struct CountRequests {
+  static constexpr int XS = 0, DS = 0, BS = kBwdBatch;
+  static constexpr bool kCount = true;
+  struct Args {
+    unsigned long long* count;
+  };
+  template <int D>
+  static constexpr void check() {
+    static_assert(D == 3, "3-D grids are instrumented");
+  }
+};
+
+// ---------------------------------------------------------------------------------------
+// Backward v2 (F = 2, L <= 16): 4 lanes per level, one chunk of K consecutive samples per
+// wave. lane = 4*level + 2*b + f owns feature f of the 2^(D-1) corners whose x-offset is b.
+// The 4 lanes of a level touch entries (x, x+1) x features (0, 1): adjacent addresses on
+// dense levels (and on hashed levels when x is even, since the first hash prime is 1),
+// so one wave instruction issues one memory request per level instead of four. When
+// the sample moves to a neighbouring cell with the same x, corners shared by the two
+// cells keep their accumulated gradient. A corner whose sum is exactly zero issues no
+// request: under build numerics such sums are rare, under the reference numerics most
+// samples' f16 dL/denc underflow to zero (tcnn's x128 loss scale rounds them away), and the
+// memory-side request count at the chunk ends alone fell from 20.8 M to 18.7 M per launch
+// after the first step (profiles/r04_close PMC). A pending sum may so arrive in two atomics
+// instead of one: f32 order, as any run.
+template <int D, typename TG, typename Walk>
 __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
     GridLevels G, int n_levels, const float* __restrict__ x, int64_t x_stride_rt, int64_t M,
     int64_t K, const TG* __restrict__ dout, int64_t dout_stride_rt, float* __restrict__ dtable,
-    int skip_zero, unsigned long long* __restrict__ count = nullptr,
-    const uint8_t* __restrict__ tile_nz = nullptr, const uint32_t* __restrict__ row_nz = nullptr) {
-  constexpr int NC = Corners<D>::NC;
+    typename Walk::Args wa) {
+  Walk::template check<D>();
+  constexpr int NC = LaneCorners<D>::NC;
+  constexpr int XS = Walk::XS, DS = Walk::DS, BS = Walk::BS;
+  constexpr bool COUNT = Walk::kCount;
   const int64_t x_stride = XS > 0 ? XS : x_stride_rt;
   const int64_t dout_stride = DS > 0 ? DS : dout_stride_rt;
   const int lane = threadIdx.x & 63;
@@ -686,7 +705,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
     if constexpr (COUNT) {
       n_req += distinct_segments(
           out, reinterpret_cast<uintptr_t>(grad + static_cast<int64_t>(e) * 2) >> 6);
-    } else if constexpr ((HASH_EXP & 1) == 0) {
+    } else {
       __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rg, out ? gbase + e * 8u : kDrop, 0, 0);
     }
   };
@@ -716,11 +735,8 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
         LaneCorners<D>::carry(acc, dl, keepx, nacc);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          // skip_zero: a leaving corner whose sum is exactly zero issues no request
-          // (reference numerics: tcnn's x128 f16 backward rounds most dL/denc to zero);
-          // without skip_zero only the leaving test applies
-          const bool out = ((!keepx) | LaneCorners<D>::leaves(c, dl)) &
-                           ((skip_zero == 0) | (acc[c] != 0.0f));
+          // a leaving corner whose sum is exactly zero issues no request
+          const bool out = ((!keepx) | LaneCorners<D>::leaves(c, dl)) & (acc[c] != 0.0f);
           flush(out, idx[c], acc[c]);
         }
 #pragma unroll
@@ -735,14 +751,13 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
     for (int c = 0; c < NC; ++c) {
       float wt = wx;
 #pragma unroll
-      for (int d = 1; d < D; ++d) wt *= Corners<D>::bit(c, d) ? w[d] : 1.0f - w[d];
+      for (int d = 1; d < D; ++d) wt *= LaneCorners<D>::bit(c, d) ? w[d] : 1.0f - w[d];
       acc[c] = fmaf(wt, gv, acc[c]);
     }
   };
 
   // Batches of BS samples: the next batch's coordinates and gradients are loaded while
   // this one is processed (indices clamped to the chunk, so the loads need no branch).
-  constexpr int BS = BSZ;
   float xb[BS][D], xn[BS][D];
   TG gb[BS], gn[BS];
   const int col = level * 2 + f;
@@ -771,14 +786,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
       }
     }
   };
-  // A batch whose dL/dy is zero in every lane (all 16 levels x 2 features of its BS
-  // samples: the reference numerics' f16 underflow leaves half of the 8-sample batches so
-  // at the bench state) adds nothing and is skipped with one test. skip_zero 2 (default)
-  // also skips single all-zero samples inside a batch and keeps the pending cell across
-  // the skipped ones; skip_zero 1 (the r04 form, A/B) walks every sample of a batch with
-  // any nonzero value and flushes at an all-zero batch as at a chunk end. Either way the
-  // same contributions reach the same entries (a pending sum may arrive in two atomics
-  // instead of one: f32 order, as any run). With skip_zero 0 (A/B) every batch is walked.
+  // the chunk's end: every held corner with a nonzero sum
   auto flush_all = [&]() {
     if (have) {
       uint32_t idx[NC];
@@ -791,22 +799,24 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
       have = false;
     }
   };
+  // A batch whose dL/dy is zero in every lane (all 16 levels x 2 features of its BS
+  // samples: the reference numerics' f16 underflow leaves half of the 8-sample batches so
+  // at the bench state) adds nothing and is skipped with one test; inside a walked batch a
+  // SAMPLE whose dL/dy row is zero in every lane is not walked either. The pending cell is
+  // kept across the skipped ones, and the walk stays exact because the next walked sample's
+  // cell test / carry handles any jump (every corner leaves when a coordinate moves by more
+  // than one cell). A pending sum may so arrive in two atomics instead of one: f32 order,
+  // as any run.
   auto do_batch = [&](int64_t mb) {
     bool nzb = false;
 #pragma unroll
     for (int j = 0; j < BS; ++j) nzb = nzb || (mb + j < m1 && to_f32<TG>(gb[j]) != 0.0f);
-    if (!skip_zero || __any(nzb)) {
+    if (__any(nzb)) {
 #pragma unroll
       for (int j = 0; j < BS; ++j) {
         const float gv = to_f32<TG>(gb[j]);
-        // skip_zero 2: a SAMPLE whose dL/dy row is zero in every lane (all levels and
-        // features) is not walked at all: it adds nothing, and the walk stays exact
-        // because the next walked sample's cell test / carry handles any jump (every
-        // corner leaves when a coordinate moves by more than one cell)
-        if (mb + j < m1 && (skip_zero < 2 || __any(gv != 0.0f))) step(xb[j], gv);
+        if (mb + j < m1 && __any(gv != 0.0f)) step(xb[j], gv);
       }
-    } else if (skip_zero == 1) {
-      flush_all();
     }
   };
   auto advance = [&]() {
@@ -817,16 +827,15 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
       for (int d = 0; d < D; ++d) xb[j][d] = xn[j][d];
     }
   };
-  if constexpr (SPARSE) {
-    static_assert(XS == 3 && DS == 32 && !COUNT, "row-mask walk: fused-field layout only");
+  // ---- the walk: three forms
+  if constexpr (std::is_same<Walk, RowBitsWalk>::value) {
+    const uint32_t* __restrict__ row_nz = wa.row_nz;
     // The chunk's set rows, compacted in order into this wave's LDS slot (K <= 256, a
     // multiple of 32; 64 rows per round: lane l tests row r0 + l), then walked in batches of
     // BS with the next batch's coordinates (scalar loads) and gradients prefetched. Every
     // loaded row is nonzero in some lane, so no per-sample test remains; the rows whose bit
     // is clear are exactly those the dense walk's per-sample skip passes over, so the same
     // corner sums reach the same entries.
-    constexpr int BS = BSZ;
-    static_assert(BS % 2 == 0, "row indices are read in pairs");
     // K <= 256 rows, then 2 BS copies of the last set row: a batch (and the prefetch past
     // the end) reads its BS indices in pairs with no clamp
     __shared__ __attribute__((aligned(16))) uint32_t sidx[4][256 + 2 * BS];
@@ -886,7 +895,8 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
         advance();
       }
     }
-  } else if (BSZ != 8 || tile_nz == nullptr) {  // the tile mask below is laid out for BS = 8
+  } else if constexpr (!std::is_same<Walk, TileMaskWalk>::value) {
+    // every row of the chunk, the next batch prefetched
     load_batch(m0, xb, gb);
     for (int64_t mb = m0; mb < m1; mb += BS) {
       load_batch(mb + BS, xn, gn);
@@ -894,13 +904,12 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
       advance();
     }
   } else {
-    // anr_hashgrid_bwd_tiles: the field backward marked the 32-row tiles whose dL/dy is
-    // zero in every row (it skipped them); their batches are neither loaded nor walked.
-    // A chunk (K <= 256 rows, a multiple of 32, tile-aligned) is <= 32 batches of 8: one
-    // wave-uniform bit mask, walked in order with the next set batch prefetched.
+    // the batches of the flagged tiles only. A chunk (K <= 256 rows, a multiple of 32,
+    // tile-aligned) is <= 32 batches of 8: one wave-uniform bit mask, walked in order with
+    // the next set batch prefetched.
     const int nbatch = static_cast<int>((m1 - m0 + BS - 1) / BS);
     const int ntile = static_cast<int>((m1 - m0 + 31) >> 5);
-    const uint8_t* tf = tile_nz + (m0 >> 5);
+    const uint8_t* tf = wa.tile_nz + (m0 >> 5);
     uint32_t bm = 0;
     for (int t = 0; t < ntile; ++t)
       if (tf[t]) bm |= 0xFu << (4 * t);
@@ -924,7 +933,7 @@ __global__ void __launch_bounds__(256) hashgrid_bwd_v2_kernel(
   flush_all();
   if constexpr (COUNT) {
     // per lane (lanes above n_levels have returned; an instrument, not the hot path)
-    if (n_req) atomicAdd(count, static_cast<unsigned long long>(n_req));
+    if (n_req) atomicAdd(wa.count, static_cast<unsigned long long>(n_req));
   }
 }
 
@@ -945,16 +954,10 @@ static int64_t pick_chunk_v2(int64_t M) {
   return K;
 }
 
-// Kernel generation per direction. Mode 0 (default): forward v6, backward v2 (measured
-// fastest on the ray-coherent bench workload; v6 falls back to v1 above 16 levels or
-// past 32-bit buffer offsets); 1: both v1 (the generic kernels every shape falls back
-// to); 6: forward v1, backward v2 (the r01 default); 7: as 0 with the backward's run-time-
-// stride instantiation (A/B of the compile-time strides). anr_hashgrid_force_v1() selects
-// it (test hook). The r02 forward experiments v2-v5
-// (x-pair lanes, batched gathers, one thread per sample, LDS-compacted gathers) measured
-// slower than v6 and were removed in r04 (profiles/r02_hash_fwd_v6_v7_ab.log). On the
-// bench coordinates the forward spends ~0.35 of its ~0.65 ms on the corner gathers' memory
-// traffic (0.29 ms with no gathers at all) and is not issue-bound.
+// anr_hashgrid_force_v1 (the tests' hook) selects the kernel generation per direction. Mode 0
+// (default): forward v6, backward v2, measured fastest on the ray-coherent bench workload; 1:
+// both v1, the generic kernels every shape falls back to; 6: forward v1, backward v2; 7: as 0
+// with the backward's run-time-stride form (A/B of the compile-time strides).
 static bool valid_mode(int m) { return m == 0 || m == 1 || m == 6 || m == 7; }
 static int g_hashgrid_mode = 0;
 static bool fwd_v6() { return g_hashgrid_mode == 0 || g_hashgrid_mode == 7; }
@@ -985,131 +988,180 @@ static int64_t pick_chunk(int64_t M, int64_t run = 0) {
   return K;
 }
 
+// 32-bit buffer offsets: a kernel that addresses through a buffer descriptor needs every one
+// of its byte ranges below 2^31 (the descriptor's range check, and the drop offset of masked
+// stores and atomics, sit at 2 GB)
+static bool fits_buffer(std::initializer_list<int64_t> byte_ranges) {
+  for (const int64_t b : byte_ranges)
+    if (b >= (int64_t{1} << 31)) return false;
+  return true;
+}
+static int64_t elem_bytes(int32_t dt) { return dt == ANR_F16 ? 2 : 4; }
+
+// The element type of a dtype code, handed to a generic callable: with_dtype(dt, [&](auto t)
+// { using T = typename decltype(t)::type; ... })
+template <typename T>
+struct Type {
+  using type = T;
+};
+template <typename Fn>
+static void with_dtype(int32_t dt, Fn fn) {
+  if (dt == ANR_F16) fn(Type<__half>{});
+  else fn(Type<float>{});
+}
+
 template <int D, int F>
 static int launch_fwd(const GridLevels& G, const anr_hashgrid_desc* d, const float* x,
                       int64_t x_stride, int64_t M, const void* table, int32_t tdt,
-                      void* out, int32_t odt, int64_t out_stride, hipStream_t s,
-                      int64_t run = 0) {
-  // 4-D runs the generic v1 walker (the v6 walker is specialised for 2 and 3 dimensions)
-  if constexpr (F == 2 && D <= 3)
-  if (d->n_levels <= 16 && fwd_v6()) {
-    // 32-bit buffer offsets: every byte range must stay below 2^31
-    const int64_t esz_t = tdt == ANR_F16 ? 2 : 4, esz_o = odt == ANR_F16 ? 2 : 4;
+                      void* out, int32_t odt, int64_t out_stride, hipStream_t s, int64_t run) {
+  const int64_t K = pick_chunk(M, run);
+  const int64_t chunks = ceil_div(M, K);
+  // v6: 2 features, 2-D or 3-D (4-D runs the generic walker), at most 16 levels, every byte
+  // range (the prefetch past the last chunk included) within a buffer descriptor
+  if constexpr (F == 2 && D <= 3) {
+    const int64_t esz_o = elem_bytes(odt);
     const int64_t x_bytes = ((M - 1) * x_stride + D) * 4;
-    const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * esz_t);
+    const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * elem_bytes(tdt));
     const int64_t o_bytes = ((M - 1) * out_stride + d->n_levels * 2) * esz_o;
-    const int64_t K = pick_chunk(M, run);
-    const int64_t lim = int64_t(1) << 31;
-    if (x_bytes < lim && t_bytes < lim && o_bytes < lim && (M + K) * x_stride * 4 < lim &&
-        (M + K) * out_stride * esz_o < lim) {
-      const int64_t chunks = ceil_div(M, K);
+    if (d->n_levels <= 16 && fwd_v6() &&
+        fits_buffer({x_bytes, t_bytes, o_bytes, (M + K) * x_stride * 4,
+                     (M + K) * out_stride * esz_o})) {
       const dim3 grid(static_cast<unsigned>(ceil_div(chunks, 16))), block(256);
-#define ANR_HG_FWD6(TT, TO)                                                                    \
-  hipLaunchKernelGGL((hashgrid_fwd_v6_kernel<D, TT, TO>), grid, block, 0, s, G, d->n_levels,   \
-                     x, static_cast<uint32_t>(x_bytes), static_cast<uint32_t>(x_stride * 4), M, \
-                     static_cast<int>(K), static_cast<const TT*>(table),                       \
-                     static_cast<uint32_t>(t_bytes), static_cast<TO*>(out),                    \
-                     static_cast<uint32_t>(o_bytes), static_cast<uint32_t>(out_stride * esz_o))
-      if (tdt == ANR_F16 && odt == ANR_F16) ANR_HG_FWD6(__half, __half);
-      else if (tdt == ANR_F16 && odt == ANR_F32) ANR_HG_FWD6(__half, float);
-      else if (tdt == ANR_F32 && odt == ANR_F16) ANR_HG_FWD6(float, __half);
-      else ANR_HG_FWD6(float, float);
-#undef ANR_HG_FWD6
+      with_dtype(tdt, [&](auto tt) {
+        with_dtype(odt, [&](auto to) {
+          using TT = typename decltype(tt)::type;
+          using TO = typename decltype(to)::type;
+          hipLaunchKernelGGL((hashgrid_fwd_v6_kernel<D, TT, TO>), grid, block, 0, s, G,
+                             d->n_levels, x, static_cast<uint32_t>(x_bytes),
+                             static_cast<uint32_t>(x_stride * 4), M, static_cast<int>(K),
+                             static_cast<const TT*>(table), static_cast<uint32_t>(t_bytes),
+                             static_cast<TO*>(out), static_cast<uint32_t>(o_bytes),
+                             static_cast<uint32_t>(out_stride * esz_o));
+        });
+      });
       ANR_CHECK_LAUNCH("anr_hashgrid_fwd(v6)");
       return ANR_OK;
     }
   }
+  // every other grid: the generic v1 walker
   const int lpw = kFwdLpw;
   const int n_groups = static_cast<int>(ceil_div(d->n_levels, lpw));
-  const int64_t K = pick_chunk(M, run);
-  const int64_t chunks = ceil_div(M, K);
   const int64_t blocks_per_group = ceil_div(ceil_div(chunks, 64 / lpw), 4);
   const dim3 grid(static_cast<unsigned>(blocks_per_group * n_groups)), block(256);
-#define ANR_HG_FWD(TT, TO)                                                                  \
-  hipLaunchKernelGGL((hashgrid_fwd_kernel<D, F, TT, TO>), grid, block, 0, s, G,             \
-                     d->n_levels, lpw, n_groups, x, x_stride, M, K,                          \
-                     static_cast<const TT*>(table), static_cast<TO*>(out), out_stride)
-  if (tdt == ANR_F16 && odt == ANR_F16) ANR_HG_FWD(__half, __half);
-  else if (tdt == ANR_F16 && odt == ANR_F32) ANR_HG_FWD(__half, float);
-  else if (tdt == ANR_F32 && odt == ANR_F16) ANR_HG_FWD(float, __half);
-  else ANR_HG_FWD(float, float);
-#undef ANR_HG_FWD
+  with_dtype(tdt, [&](auto tt) {
+    with_dtype(odt, [&](auto to) {
+      using TT = typename decltype(tt)::type;
+      using TO = typename decltype(to)::type;
+      hipLaunchKernelGGL((hashgrid_fwd_kernel<D, F, TT, TO>), grid, block, 0, s, G, d->n_levels,
+                         lpw, n_groups, x, x_stride, M, K, static_cast<const TT*>(table),
+                         static_cast<TO*>(out), out_stride);
+    });
+  });
   ANR_CHECK_LAUNCH("anr_hashgrid_fwd");
   return ANR_OK;
 }
-
-// Cell-move flushes skip corners whose sum is exactly zero (the chunk-end flush always
-// did). Under build numerics such sums are rare and the test is pure cost; under the
-// reference numerics most samples' f16 dL/denc underflow to zero (tcnn's x128 loss scale
-// rounds them away), and the memory-side request count at the chunk ends alone fell from
-// 20.8 M to 18.7 M per launch after the first step (profiles/r04_close PMC).
-// The kernel's skip_zero argument takes 0 (off), 1 (the cell-move flushes) or 2 (also a
-// per-sample skip of all-zero dL/dy rows, r05); every launch passes 2.
-constexpr int kBwdSkipZero = 2;
 
 // The v2 backward walker's grids: 2 features, at most 16 levels, 2-D or 3-D (LaneCorners,
 // its corner carry, has no 4-D form), and not switched off by anr_hashgrid_force_v1 ...
 static bool bwd_v2_shape(const anr_hashgrid_desc* d) {
   return d->n_features == 2 && d->n_dims <= 3 && d->n_levels <= 16 && bwd_v2();
 }
-// ... and a gradient table below 2 GB: v2 addresses it through a buffer descriptor (32-bit
-// byte offsets, the drop offset at 2 GB), so larger tables (2^24 entries x 16 levels) take
-// the v1 walker
+// ... and a gradient table within a buffer descriptor: larger tables (2^24 entries x 16
+// levels) take the v1 walker
 static bool bwd_v2_takes(const anr_hashgrid_desc* d, const GridLevels& G) {
-  return bwd_v2_shape(d) && table_bytes(G, d->n_levels, 2 * 4) < (int64_t{1} << 31);
+  return bwd_v2_shape(d) && fits_buffer({table_bytes(G, d->n_levels, 2 * 4)});
+}
+// The fused field's layout: 3-D coordinates in rows of 3, dL/denc in rows of 32
+static bool fused_layout(const anr_hashgrid_desc* d, int64_t x_stride, int64_t dout_stride) {
+  return d->n_dims == 3 && x_stride == 3 && dout_stride == 32;
 }
 
 // One launch of the v2 walker over chunks of K rows, a chunk per wavefront, dL/dy in f16 or
-// f32. XS, DS: compile-time strides (0: the run-time ones).
-template <int D, int XS, int DS, bool COUNT = false, int BSZ = HASH_BS, bool SPARSE = false>
+// f32; wa: what the walk takes beyond the common arguments.
+template <int D, typename Walk>
 static void launch_bwd_v2(const GridLevels& G, const anr_hashgrid_desc* d, const float* x,
                           int64_t x_stride, int64_t M, int64_t K, const void* dout, int32_t gdt,
                           int64_t dout_stride, float* dtable, hipStream_t s,
-                          unsigned long long* count = nullptr, const uint8_t* tile_nz = nullptr,
-                          const uint32_t* row_nz = nullptr) {
+                          typename Walk::Args wa = {}) {
   const dim3 grid(static_cast<unsigned>(ceil_div(ceil_div(M, K), 4))), block(256);
-  if (gdt == ANR_F16)
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, __half, XS, DS, COUNT, BSZ, SPARSE>), grid,
-                       block, 0, s, G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const __half*>(dout), dout_stride, dtable, kBwdSkipZero, count,
-                       tile_nz, row_nz);
-  else
-    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, float, XS, DS, COUNT, BSZ, SPARSE>), grid,
-                       block, 0, s, G, d->n_levels, x, x_stride, M, K,
-                       static_cast<const float*>(dout), dout_stride, dtable, kBwdSkipZero, count,
-                       tile_nz, row_nz);
+  with_dtype(gdt, [&](auto tg) {
+    using TG = typename decltype(tg)::type;
+    hipLaunchKernelGGL((hashgrid_bwd_v2_kernel<D, TG, Walk>), grid, block, 0, s, G, d->n_levels,
+                       x, x_stride, M, K, static_cast<const TG*>(dout), dout_stride, dtable, wa);
+  });
 }
 
 template <int D, int F>
 static int launch_bwd(const GridLevels& G, const anr_hashgrid_desc* d, const float* x,
                       int64_t x_stride, int64_t M, const void* dout, int32_t gdt,
                       int64_t dout_stride, float* dtable, hipStream_t s) {
-  // every other grid runs the generic v1 walker
-  if constexpr (F == 2 && D <= 3)
-  if (bwd_v2_takes(d, G)) {
-    const int64_t K = pick_chunk_v2(M);
-    // compile-time strides for the fused field's layout ((M,3) coordinates, (M,32) dL/denc)
-    if (D == 3 && x_stride == 3 && dout_stride == 32 && g_hashgrid_mode != 7)
-      launch_bwd_v2<D, 3, 32>(G, d, x, x_stride, M, K, dout, gdt, dout_stride, dtable, s);
-    else
-      launch_bwd_v2<D, 0, 0>(G, d, x, x_stride, M, K, dout, gdt, dout_stride, dtable, s);
-    ANR_CHECK_LAUNCH("anr_hashgrid_bwd(v2)");
-    return ANR_OK;
+  if constexpr (F == 2 && D <= 3) {
+    if (bwd_v2_takes(d, G)) {
+      const int64_t K = pick_chunk_v2(M);
+      bool fused = false;
+      if constexpr (D == 3) {
+        // compile-time strides for the fused field's layout (mode 7: A/B against the run-time ones)
+        fused = fused_layout(d, x_stride, dout_stride) && g_hashgrid_mode != 7;
+        if (fused)
+          launch_bwd_v2<D, DenseWalk<3, 32>>(G, d, x, x_stride, M, K, dout, gdt, dout_stride,
+                                             dtable, s);
+      }
+      if (!fused)
+        launch_bwd_v2<D, DenseWalk<0, 0>>(G, d, x, x_stride, M, K, dout, gdt, dout_stride,
+                                          dtable, s);
+      ANR_CHECK_LAUNCH("anr_hashgrid_bwd(v2)");
+      return ANR_OK;
+    }
   }
+  // every other grid: the generic v1 walker
   const int lpc = d->n_levels <= 16 ? 16 : 32;
   const int64_t K = pick_chunk(M);
-  const int64_t chunks = ceil_div(M, K);
-  const int64_t threads = chunks * lpc;
+  const int64_t threads = ceil_div(M, K) * lpc;
   const dim3 grid(static_cast<unsigned>(ceil_div(threads, 256))), block(256);
-  if (gdt == ANR_F16)
-    hipLaunchKernelGGL((hashgrid_bwd_kernel<D, F, __half>), grid, block, 0, s, G,
-                       d->n_levels, lpc, x, x_stride, M, K,
-                       static_cast<const __half*>(dout), dout_stride, dtable);
-  else
-    hipLaunchKernelGGL((hashgrid_bwd_kernel<D, F, float>), grid, block, 0, s, G,
-                       d->n_levels, lpc, x, x_stride, M, K,
-                       static_cast<const float*>(dout), dout_stride, dtable);
+  with_dtype(gdt, [&](auto tg) {
+    using TG = typename decltype(tg)::type;
+    hipLaunchKernelGGL((hashgrid_bwd_kernel<D, F, TG>), grid, block, 0, s, G, d->n_levels, lpc,
+                       x, x_stride, M, K, static_cast<const TG*>(dout), dout_stride, dtable);
+  });
   ANR_CHECK_LAUNCH("anr_hashgrid_bwd");
+  return ANR_OK;
+}
+
+// fn(D, F) as integral constants for the descriptor's (n_dims, n_features)
+template <int... Vs, typename Fn>
+static bool with_int(int v, Fn fn) {
+  return ((v == Vs ? (fn(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <typename Fn>
+static int with_shape(const anr_hashgrid_desc* d, Fn fn) {
+  int rc = ANR_E_UNSUPPORTED;
+  bool found = false;
+  with_int<2, 3, 4>(d->n_dims, [&](auto dims) {
+    found = with_int<1, 2, 4, 8>(d->n_features, [&](auto feats) { rc = fn(dims, feats); });
+  });
+  if (!found)
+    set_error("hashgrid: unsupported n_dims=%d n_features=%d", d->n_dims, d->n_features);
+  return rc;
+}
+
+static bool is_float(int32_t dt) { return dt == ANR_F16 || dt == ANR_F32; }
+
+// The argument check of every entry point, each message under the entry's own name `fn`:
+// pointers, row count and strides (row_min: the least row_stride, 0 = the grid's n_levels x
+// n_features values; hint: appended to the shape message), dtypes. The level tables follow
+// (check_levels), after whatever an entry point checks in between.
+static int check_call(const char* fn, const anr_hashgrid_desc* d, bool pointers, int64_t M,
+                      int64_t x_stride, int64_t row_stride, int64_t row_min, bool dtypes,
+                      const char* hint = "") {
+  ANR_CHECK_ARG(d && pointers, "%s: null argument", fn);
+  if (row_min == 0) row_min = static_cast<int64_t>(d->n_levels) * d->n_features;
+  ANR_CHECK_ARG(M >= 0 && x_stride >= d->n_dims && row_stride >= row_min,
+                "%s: bad shape/stride%s", fn, hint);
+  ANR_CHECK_ARG(dtypes, "%s: bad dtype", fn);
+  return ANR_OK;
+}
+static int check_levels(const char* fn, const anr_hashgrid_desc* d, GridLevels* G) {
+  ANR_CHECK_ARG(make_levels(d, G), "%s: descriptor not initialised", fn);
   return ANR_OK;
 }
 
@@ -1190,56 +1242,34 @@ extern "C" int anr_hashgrid_init_nd(anr_hashgrid_desc* d, int32_t n_dims, int32_
                        log2_hashmap_size);
 }
 
-#define ANR_HG_DISPATCH(FN, ...)                                                   \
-  switch (d->n_dims * 16 + d->n_features) {                                        \
-    case 2 * 16 + 1: return FN<2, 1>(__VA_ARGS__);                                 \
-    case 2 * 16 + 2: return FN<2, 2>(__VA_ARGS__);                                 \
-    case 2 * 16 + 4: return FN<2, 4>(__VA_ARGS__);                                 \
-    case 2 * 16 + 8: return FN<2, 8>(__VA_ARGS__);                                 \
-    case 3 * 16 + 1: return FN<3, 1>(__VA_ARGS__);                                 \
-    case 3 * 16 + 2: return FN<3, 2>(__VA_ARGS__);                                 \
-    case 3 * 16 + 4: return FN<3, 4>(__VA_ARGS__);                                 \
-    case 3 * 16 + 8: return FN<3, 8>(__VA_ARGS__);                                 \
-    case 4 * 16 + 1: return FN<4, 1>(__VA_ARGS__);                                 \
-    case 4 * 16 + 2: return FN<4, 2>(__VA_ARGS__);                                 \
-    case 4 * 16 + 4: return FN<4, 4>(__VA_ARGS__);                                 \
-    case 4 * 16 + 8: return FN<4, 8>(__VA_ARGS__);                                 \
-    default:                                                                       \
-      ::anr::set_error("hashgrid: unsupported n_dims=%d n_features=%d", d->n_dims, \
-                       d->n_features);                                             \
-      return ANR_E_UNSUPPORTED;                                                    \
-  }
-
 extern "C" int anr_hashgrid_bwd_count_requests(const anr_hashgrid_desc* d, const float* x,
                                                int64_t x_stride, int64_t M, const void* dout,
                                                int32_t dout_dtype, int64_t dout_stride,
                                                const float* dtable, unsigned long long* count,
                                                anr_stream_t stream) {
   using namespace anr;
-  ANR_CHECK_ARG(d && x && dout && dtable && count, "anr_hashgrid_bwd_count_requests: null argument");
-  ANR_CHECK_ARG(M >= 0 && x_stride >= d->n_dims && dout_stride >= (int64_t)d->n_levels * d->n_features,
-                "anr_hashgrid_bwd_count_requests: bad shape/stride");
-  ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32,
-                "anr_hashgrid_bwd_count_requests: bad dtype");
+  constexpr const char* fn = "anr_hashgrid_bwd_count_requests";
+  if (const int rc = check_call(fn, d, x && dout && dtable && count, M, x_stride, dout_stride, 0,
+                                is_float(dout_dtype)))
+    return rc;
   if (!(d->n_dims == 3 && bwd_v2_shape(d))) {
-    set_error("anr_hashgrid_bwd_count_requests: only the v2 backward (3-D, 2 features, <= 16 "
-              "levels) is instrumented");
+    set_error("%s: only the v2 backward (3-D, 2 features, <= 16 levels) is instrumented", fn);
     return ANR_E_UNSUPPORTED;
   }
   GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_count_requests: descriptor not initialised");
+  if (const int rc = check_levels(fn, d, &G)) return rc;
   // gradient tables of 2 GB or more take the v1 walker in launch_bwd, whose requests this
   // v2 instrument does not model
   if (!bwd_v2_takes(d, G)) {
-    set_error("anr_hashgrid_bwd_count_requests: gradient table of 2 GB or more (the backward "
-              "runs the uninstrumented v1 walker there)");
+    set_error("%s: gradient table of 2 GB or more (the backward runs the uninstrumented v1 "
+              "walker there)", fn);
     return ANR_E_UNSUPPORTED;
   }
   if (M == 0) return ANR_OK;
-  float* tab = const_cast<float*>(dtable);  // not written in COUNT mode
-  launch_bwd_v2<3, 0, 0, true>(G, d, x, x_stride, M, pick_chunk_v2(M), dout, dout_dtype,
-                               dout_stride, tab, as_stream(stream), count);
-  ANR_CHECK_LAUNCH("anr_hashgrid_bwd_count_requests");
+  float* tab = const_cast<float*>(dtable);  // not written by this walk
+  launch_bwd_v2<3, CountRequests>(G, d, x, x_stride, M, pick_chunk_v2(M), dout, dout_dtype,
+                                  dout_stride, tab, as_stream(stream), {count});
+  ANR_CHECK_LAUNCH(fn);
   return ANR_OK;
 }
 
@@ -1247,35 +1277,41 @@ extern "C" int64_t anr_hashgrid_bwd_chunk(int64_t M) {
   return M > 0 ? anr::pick_chunk_v2(M) : 0;
 }
 
+// anr_hashgrid_fwd and anr_hashgrid_fwd_runs under the name fn
+static int hashgrid_fwd(const char* fn, const anr_hashgrid_desc* d, const float* x,
+                        int64_t x_stride, int64_t M, int64_t run_length, const void* table,
+                        int32_t table_dtype, void* out, int32_t out_dtype, int64_t out_stride,
+                        anr_stream_t stream) {
+  using namespace anr;
+  if (M == 0) return ANR_OK;
+  ANR_CHECK_ARG(d && x && table && out, "%s: null argument", fn);
+  ANR_CHECK_ARG(run_length >= 0, "%s: run_length %lld < 0", fn, (long long)run_length);
+  if (const int rc = check_call(fn, d, true, M, x_stride, out_stride, 0,
+                                is_float(table_dtype) && is_float(out_dtype)))
+    return rc;
+  GridLevels G;
+  if (const int rc = check_levels(fn, d, &G)) return rc;
+  return with_shape(d, [&](auto dims, auto feats) {
+    return launch_fwd<dims(), feats()>(G, d, x, x_stride, M, table, table_dtype, out, out_dtype,
+                                       out_stride, as_stream(stream), run_length);
+  });
+}
+
 extern "C" int anr_hashgrid_fwd_runs(const anr_hashgrid_desc* d, const float* x,
                                      int64_t x_stride, int64_t M, int64_t run_length,
                                      const void* table, int32_t table_dtype, void* out,
                                      int32_t out_dtype, int64_t out_stride,
                                      anr_stream_t stream) {
-  using namespace anr;
-  if (M == 0) return ANR_OK;
-  ANR_CHECK_ARG(d && x && table && out, "anr_hashgrid_fwd: null argument");
-  ANR_CHECK_ARG(run_length >= 0, "anr_hashgrid_fwd_runs: run_length %lld < 0",
-                (long long)run_length);
-  ANR_CHECK_ARG(M >= 0 && x_stride >= d->n_dims &&
-                    out_stride >= (int64_t)d->n_levels * d->n_features,
-                "anr_hashgrid_fwd: bad shape/stride");
-  ANR_CHECK_ARG((table_dtype == ANR_F16 || table_dtype == ANR_F32) &&
-                    (out_dtype == ANR_F16 || out_dtype == ANR_F32),
-                "anr_hashgrid_fwd: bad dtype");
-  if (M == 0) return ANR_OK;
-  GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_fwd: descriptor not initialised");
-  ANR_HG_DISPATCH(launch_fwd, G, d, x, x_stride, M, table, table_dtype, out, out_dtype,
-                  out_stride, as_stream(stream), run_length);
+  return hashgrid_fwd("anr_hashgrid_fwd_runs", d, x, x_stride, M, run_length, table, table_dtype,
+                      out, out_dtype, out_stride, stream);
 }
 
 extern "C" int anr_hashgrid_fwd(const anr_hashgrid_desc* d, const float* x,
                                 int64_t x_stride, int64_t M, const void* table,
                                 int32_t table_dtype, void* out, int32_t out_dtype,
                                 int64_t out_stride, anr_stream_t stream) {
-  return anr_hashgrid_fwd_runs(d, x, x_stride, M, 0, table, table_dtype, out, out_dtype,
-                               out_stride, stream);
+  return hashgrid_fwd("anr_hashgrid_fwd", d, x, x_stride, M, 0, table, table_dtype, out,
+                      out_dtype, out_stride, stream);
 }
 
 extern "C" int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* x,
@@ -1283,49 +1319,38 @@ extern "C" int anr_hashgrid_fwd_planes(const anr_hashgrid_desc* d, const float* 
                                        int32_t table_dtype, void* out, int64_t plane_stride,
                                        anr_stream_t stream) {
   using namespace anr;
+  constexpr const char* fn = "anr_hashgrid_fwd_planes";
   if (M == 0) return ANR_OK;
-  ANR_CHECK_ARG(d && x && table && out, "anr_hashgrid_fwd_planes: null argument");
-  ANR_CHECK_ARG(M > 0 && x_stride >= d->n_dims && plane_stride >= 8 * M,
-                "anr_hashgrid_fwd_planes: bad shape/stride (plane_stride >= 8 M)");
+  // a plane holds 8 values per row; the alignment is tested between shape and dtype
+  if (const int rc = check_call(fn, d, x && table && out, M, x_stride, plane_stride, 8 * M, true,
+                                " (plane_stride >= 8 M)"))
+    return rc;
   ANR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (plane_stride & 7) == 0,
-                "anr_hashgrid_fwd_planes: out and plane_stride must be 16-byte aligned");
-  ANR_CHECK_ARG(table_dtype == ANR_F16 || table_dtype == ANR_F32,
-                "anr_hashgrid_fwd_planes: bad dtype");
+                "%s: out and plane_stride must be 16-byte aligned", fn);
+  ANR_CHECK_ARG(is_float(table_dtype), "%s: bad dtype", fn);
   ANR_CHECK_ARG(d->n_features == 2 && d->n_levels <= 16 && d->n_dims >= 2 && d->n_dims <= 4,
-                "anr_hashgrid_fwd_planes: 2 features, <= 16 levels, 2-D to 4-D");
+                "%s: 2 features, <= 16 levels, 2-D to 4-D", fn);
   GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_fwd_planes: descriptor not initialised");
-  const int64_t esz_t = table_dtype == ANR_F16 ? 2 : 4;
+  if (const int rc = check_levels(fn, d, &G)) return rc;
   const int64_t n_quads = (d->n_levels + 3) / 4;
   const int64_t x_bytes = ((M - 1) * x_stride + d->n_dims) * 4;
-  const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * esz_t);
+  const int64_t t_bytes = table_bytes(G, d->n_levels, 2 * elem_bytes(table_dtype));
   const int64_t o_bytes = ((n_quads - 1) * plane_stride + 8 * M) * 2;
-  const int64_t lim = int64_t(1) << 31;
-  ANR_CHECK_ARG(x_bytes < lim && t_bytes < lim && o_bytes < lim &&
-                    (M + 256) * x_stride * 4 < lim && plane_stride * 2 < lim,
-                "anr_hashgrid_fwd_planes: byte ranges must stay below 2^31");
+  ANR_CHECK_ARG(fits_buffer({x_bytes, t_bytes, o_bytes, (M + 256) * x_stride * 4,
+                             plane_stride * 2}),
+                "%s: byte ranges must stay below 2^31", fn);
   const dim3 grid(static_cast<unsigned>(ceil_div(M, 256))), block(256);
-  // run-leader gathers (plane_quad) at every level, HASH_DEDUP = 64: the largest number of
-  // cell changes per wavefront at which a level gathers at the run leaders only. Measured on
-  // the settled bench step, hash fwd 0.478 ms with them off, 0.435 / 0.439 / 0.433 / 0.421 ms
-  // at 32 / 16 / 48 / 64 (profiles/r06_hash_fwd_dedup_sweep.log)
-#define ANR_HG_PL1(D_, TT)                                                                   \
-  hipLaunchKernelGGL((hashgrid_fwd_planes_kernel<D_, TT, HASH_DEDUP>), grid, block, 0,       \
-                     as_stream(stream), G, d->n_levels, x, static_cast<uint32_t>(x_bytes),   \
-                     static_cast<uint32_t>(x_stride * 4), M, static_cast<const TT*>(table),  \
-                     static_cast<uint32_t>(t_bytes), static_cast<__half*>(out),              \
-                     static_cast<uint32_t>(o_bytes), static_cast<uint32_t>(plane_stride * 2))
-#define ANR_HG_PL(D_)                                                                        \
-  do {                                                                                       \
-    if (table_dtype == ANR_F16) ANR_HG_PL1(D_, __half);                                      \
-    else ANR_HG_PL1(D_, float);                                                              \
-  } while (0)
-  if (d->n_dims == 4) ANR_HG_PL(4);
-  else if (d->n_dims == 3) ANR_HG_PL(3);
-  else ANR_HG_PL(2);
-#undef ANR_HG_PL
-#undef ANR_HG_PL1
-  ANR_CHECK_LAUNCH("anr_hashgrid_fwd_planes");
+  with_int<2, 3, 4>(d->n_dims, [&](auto dims) {
+    with_dtype(table_dtype, [&](auto tt) {
+      using TT = typename decltype(tt)::type;
+      hipLaunchKernelGGL((hashgrid_fwd_planes_kernel<dims(), TT>), grid, block, 0,
+                         as_stream(stream), G, d->n_levels, x, static_cast<uint32_t>(x_bytes),
+                         static_cast<uint32_t>(x_stride * 4), M, static_cast<const TT*>(table),
+                         static_cast<uint32_t>(t_bytes), static_cast<__half*>(out),
+                         static_cast<uint32_t>(o_bytes), static_cast<uint32_t>(plane_stride * 2));
+    });
+  });
+  ANR_CHECK_LAUNCH(fn);
   return ANR_OK;
 }
 
@@ -1334,23 +1359,21 @@ extern "C" int anr_hashgrid_bwd_tiles(const anr_hashgrid_desc* d, const float* x
                                       int32_t dout_dtype, int64_t dout_stride, float* dtable,
                                       const uint8_t* tile_nz, anr_stream_t stream) {
   using namespace anr;
+  constexpr const char* fn = "anr_hashgrid_bwd_tiles";
   if (M == 0) return ANR_OK;
-  ANR_CHECK_ARG(d && x && dout && dtable && tile_nz, "anr_hashgrid_bwd_tiles: null argument");
-  ANR_CHECK_ARG(M > 0 && x_stride >= d->n_dims &&
-                    dout_stride >= (int64_t)d->n_levels * d->n_features,
-                "anr_hashgrid_bwd_tiles: bad shape/stride");
-  ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32, "anr_hashgrid_bwd_tiles: bad dtype");
+  if (const int rc = check_call(fn, d, x && dout && dtable && tile_nz, M, x_stride, dout_stride,
+                                0, is_float(dout_dtype)))
+    return rc;
   GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_tiles: descriptor not initialised");
+  if (const int rc = check_levels(fn, d, &G)) return rc;
   const int64_t K = pick_chunk_v2(M);
-  if (!(d->n_dims == 3 && bwd_v2_takes(d, G) && K % 32 == 0 && x_stride == 3 &&
-        dout_stride == 32)) {
+  if (!(fused_layout(d, x_stride, dout_stride) && bwd_v2_takes(d, G) && K % 32 == 0)) {
     // outside the tiled walker's shapes: the flags are an optimisation only
     return anr_hashgrid_bwd(d, x, x_stride, M, dout, dout_dtype, dout_stride, dtable, stream);
   }
-  launch_bwd_v2<3, 3, 32, false, 8>(G, d, x, x_stride, M, K, dout, dout_dtype, dout_stride,
-                                    dtable, as_stream(stream), nullptr, tile_nz);
-  ANR_CHECK_LAUNCH("anr_hashgrid_bwd_tiles");
+  launch_bwd_v2<3, TileMaskWalk>(G, d, x, x_stride, M, K, dout, dout_dtype, dout_stride, dtable,
+                                 as_stream(stream), {tile_nz});
+  ANR_CHECK_LAUNCH(fn);
   return ANR_OK;
 }
 
@@ -1374,39 +1397,35 @@ extern "C" int anr_hashgrid_bwd_rows(const anr_hashgrid_desc* d, const float* x,
                                      int32_t dout_dtype, int64_t dout_stride, float* dtable,
                                      const uint32_t* row_nz, anr_stream_t stream) {
   using namespace anr;
+  constexpr const char* fn = "anr_hashgrid_bwd_rows";
   if (M == 0) return ANR_OK;
-  ANR_CHECK_ARG(d && x && dout && dtable && row_nz, "anr_hashgrid_bwd_rows: null argument");
-  ANR_CHECK_ARG(M > 0 && x_stride >= d->n_dims &&
-                    dout_stride >= (int64_t)d->n_levels * d->n_features,
-                "anr_hashgrid_bwd_rows: bad shape/stride");
-  ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32, "anr_hashgrid_bwd_rows: bad dtype");
+  if (const int rc = check_call(fn, d, x && dout && dtable && row_nz, M, x_stride, dout_stride,
+                                0, is_float(dout_dtype)))
+    return rc;
   GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd_rows: descriptor not initialised");
+  if (const int rc = check_levels(fn, d, &G)) return rc;
   // chunks of whole 32-row words (the rule's length rounded down, at least one word)
   int64_t K = pick_chunk_v2(M) / 32 * 32;
   if (K < 32) K = 32;
   if (K > 256) K = 256;
-  if (!(d->n_dims == 3 && bwd_v2_takes(d, G) && d->n_levels == 16 && x_stride == 3 &&
-        dout_stride == 32 && M < (int64_t{1} << 31))) {
+  if (!(fused_layout(d, x_stride, dout_stride) && bwd_v2_takes(d, G) && d->n_levels == 16 &&
+        M < (int64_t{1} << 31))) {
     // outside the row-mask walker's shapes: the clear rows are zeroed in place, then the
     // dense walker reads every row
     const int ncol = d->n_levels * d->n_features;
     const int64_t nb = ceil_div(M * ncol, 256), blocks = nb < 4096 ? nb : 4096;
-    if (dout_dtype == ANR_F16)
-      hipLaunchKernelGGL(zero_clear_rows_kernel<__half>, dim3(static_cast<unsigned>(blocks)),
-                         dim3(256), 0, as_stream(stream), static_cast<__half*>(dout), dout_stride,
-                         M, ncol, row_nz);
-    else
-      hipLaunchKernelGGL(zero_clear_rows_kernel<float>, dim3(static_cast<unsigned>(blocks)),
-                         dim3(256), 0, as_stream(stream), static_cast<float*>(dout), dout_stride,
-                         M, ncol, row_nz);
+    with_dtype(dout_dtype, [&](auto tg) {
+      using TG = typename decltype(tg)::type;
+      hipLaunchKernelGGL(zero_clear_rows_kernel<TG>, dim3(static_cast<unsigned>(blocks)),
+                         dim3(256), 0, as_stream(stream), static_cast<TG*>(dout), dout_stride, M,
+                         ncol, row_nz);
+    });
     ANR_CHECK_LAUNCH("anr_hashgrid_bwd_rows(zero)");
     return anr_hashgrid_bwd(d, x, x_stride, M, dout, dout_dtype, dout_stride, dtable, stream);
   }
-  launch_bwd_v2<3, 3, 32, false, HASH_BS, true>(G, d, x, x_stride, M, K, dout, dout_dtype,
-                                                dout_stride, dtable, as_stream(stream), nullptr,
-                                                nullptr, row_nz);
-  ANR_CHECK_LAUNCH("anr_hashgrid_bwd_rows");
+  launch_bwd_v2<3, RowBitsWalk>(G, d, x, x_stride, M, K, dout, dout_dtype, dout_stride, dtable,
+                                as_stream(stream), {row_nz});
+  ANR_CHECK_LAUNCH(fn);
   return ANR_OK;
 }
 
@@ -1416,14 +1435,14 @@ extern "C" int anr_hashgrid_bwd(const anr_hashgrid_desc* d, const float* x,
                                 anr_stream_t stream) {
   using namespace anr;
   if (M == 0) return ANR_OK;
-  ANR_CHECK_ARG(d && x && dout && dtable, "anr_hashgrid_bwd: null argument");
-  ANR_CHECK_ARG(M >= 0 && x_stride >= d->n_dims &&
-                    dout_stride >= (int64_t)d->n_levels * d->n_features,
-                "anr_hashgrid_bwd: bad shape/stride");
-  ANR_CHECK_ARG(dout_dtype == ANR_F16 || dout_dtype == ANR_F32, "anr_hashgrid_bwd: bad dtype");
-  if (M == 0) return ANR_OK;
+  constexpr const char* fn = "anr_hashgrid_bwd";
+  if (const int rc = check_call(fn, d, x && dout && dtable, M, x_stride, dout_stride, 0,
+                                is_float(dout_dtype)))
+    return rc;
   GridLevels G;
-  ANR_CHECK_ARG(make_levels(d, &G), "anr_hashgrid_bwd: descriptor not initialised");
-  ANR_HG_DISPATCH(launch_bwd, G, d, x, x_stride, M, dout, dout_dtype, dout_stride, dtable,
-                  as_stream(stream));
+  if (const int rc = check_levels(fn, d, &G)) return rc;
+  return with_shape(d, [&](auto dims, auto feats) {
+    return launch_bwd<dims(), feats()>(G, d, x, x_stride, M, dout, dout_dtype, dout_stride,
+                                       dtable, as_stream(stream));
+  });
 }

@@ -1231,6 +1231,63 @@ def test_hashgrid_fwd_v6_outside_grid_and_strides(dev, cfg, M, xs, tdt):
         assert torch.all(pl[q * plane + 8 * M:(q + 1) * plane] == -9)
 
 
+@pytest.mark.parametrize("cfg,M,xs,ds", [((3, 6, 4, 2.0, 10), 5001, 3, 12),
+                                         ((2, 16, 16, 1.3819, 19), 4097, 2, 32),
+                                         ((3, 16, 16, 1.3819, 19), 2049, 3, 32),
+                                         ((3, 16, 16, 1.3819, 19), 2049, 4, 35)])
+def test_hashgrid_bwd_outside_grid_and_strides(dev, cfg, M, xs, ds):
+    """The v2 backward walker against the generic one (mode 1: grid_index per corner) off
+    the grid, the forward test's coordinates: origins in [-0.5, 1.5] (dense corner sums
+    reach T, negative cells), every 7th row clamped onto the faces, f32 dL/dy with every
+    5th row zero. All levels dense (6 levels of base 4), the 2-D run-time-stride form, the
+    fused-layout form (strides 3 / 32) and rows wider than the data (4 / 35). On the fused
+    layout also anr_hashgrid_bwd_rows with the bits of the nonzero rows and
+    anr_hashgrid_bwd_tiles with every flag set (at this size its chunks are shorter than a
+    tile, so it runs the plain walker). Equal up to the f32 atomic order; the words before
+    and after the table stay as they were."""
+    from atmonr_amd import _lib
+
+    D, L = cfg[0], cfg[1]
+    d = _lib.hashgrid_desc(D, L, 2, cfg[2], cfg[3], cfg[4])
+    gen = torch.Generator(device=dev).manual_seed(11)
+    R = -(-M // 97)
+    o = torch.rand(R, 1, D, device=dev, generator=gen) * 2.0 - 0.5
+    dr = (torch.rand(R, 1, D, device=dev, generator=gen) - 0.5) * 0.4
+    t = torch.linspace(0, 1, 97, device=dev)[None, :, None]
+    x = torch.zeros(M, xs, device=dev)
+    x[:, :D] = (o + dr * t).reshape(-1, D)[:M]
+    x[::7, :D] = x[::7, :D].clamp(0, 1)  # exact faces too
+    dout = torch.zeros(M, ds, device=dev)
+    dout[:, :2 * L] = torch.randn(M, 2 * L, device=dev, generator=gen) * 1e-3
+    dout[::5] = 0.0
+    lib = _lib.load()
+    s = _lib.stream(dev)
+    guard = 16
+
+    def walk(name, mode, *extra):
+        buf = torch.zeros(d.n_params + 2 * guard, device=dev)
+        buf[:guard] = -9.0
+        buf[guard + d.n_params:] = -9.0
+        prev = lib.anr_hashgrid_force_v1(mode)
+        try:
+            _lib.call(name, ctypes.byref(d), x.data_ptr(), xs, M, dout.data_ptr(), _lib.F32, ds,
+                      buf[guard:].data_ptr(), *extra, s)
+            torch.cuda.synchronize()
+        finally:
+            lib.anr_hashgrid_force_v1(prev)
+        assert torch.all(buf[:guard] == -9) and torch.all(buf[guard + d.n_params:] == -9)
+        return buf[guard:guard + d.n_params]
+
+    ref = walk("anr_hashgrid_bwd", 1)
+    assert (ref != 0).any()
+    close(walk("anr_hashgrid_bwd", 0), ref, rel=1e-5, atol=1e-5)
+    if (xs, ds) == (3, 32):
+        bits = _row_bits(dout).to(dev)
+        close(walk("anr_hashgrid_bwd_rows", 0, bits.data_ptr()), ref, rel=1e-5, atol=1e-5)
+        flags = torch.ones(-(-M // 32), device=dev, dtype=torch.uint8)
+        close(walk("anr_hashgrid_bwd_tiles", 0, flags.data_ptr()), ref, rel=1e-5, atol=1e-5)
+
+
 @pytest.mark.parametrize("mma,ref", [("f16", False), ("bf16", False), ("f16", True)])
 @pytest.mark.parametrize("n_per_ray,R,extra", [(1024, 5, 0), (64, 9, 13)])
 def test_ingp_field_enc_quad_planes_equal_rows(dev, mma, ref, n_per_ray, R, extra):

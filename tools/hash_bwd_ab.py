@@ -1,9 +1,10 @@
 """A/B of the hash-grid backward generations at bench size (profiling aid).
 
-    python tools/hash_bwd_ab.py [--modes 0,1] [--iters 10]
+    python tools/hash_bwd_ab.py [--modes 0,1] [--iters 10] [--grad f16] [--rows] [--dims 2]
 
 Bench coordinates (synthetic HARP2 scene -> fused sampler, 8192 rays x 1024 samples), f32
-dL/denc, f32 gradient table. Prints the HIP-event average per mode and the relative L2
+(or f16) dL/denc, f32 gradient table; --rows: anr_hashgrid_bwd_rows with ~70 % of the rows
+zero in runs and the bits of the nonzero rows (the row-bits walk). Prints the HIP-event average per mode and the relative L2
 difference of each mode's gradient from the first mode's. (The r02 log's mode 8, the
 segment-flush backward v3, was removed from the library after measuring it.)
 """
@@ -30,6 +31,9 @@ def main():
     ap.add_argument("--samples", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--modes", default="0,1")
+    ap.add_argument("--grad", choices=["f32", "f16"], default="f32")
+    ap.add_argument("--rows", action="store_true")
+    ap.add_argument("--dims", type=int, choices=[2, 3], default=3)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -43,9 +47,21 @@ def main():
     batch = next(iter(BatchLoader(ds, B, shuffle=True, seed=0)))
     prep = ds.get_point_preprocessor("horizontal").params(ngp_remap=True, alt_compress=8.0)
     _, _, coords = sample_and_preprocess(batch, N, prep)
-    x = coords.reshape(M, 3).contiguous()
-    desc = _lib.hashgrid_desc(3, 16, 2, 16, 1.3819, 19)
+    D = args.dims  # 2: the first two coordinates, rows of 2 (the run-time-stride form)
+    x = coords.reshape(M, 3)[:, :D].contiguous()
+    desc = _lib.hashgrid_desc(D, 16, 2, 16, 1.3819, 19)
     denc = torch.randn(M, 32, device=dev) * 1e-3
+    gdt = _lib.F32
+    if args.grad == "f16":
+        denc, gdt = denc.half(), _lib.F16
+    extra, entry = (), "anr_hashgrid_bwd"
+    if args.rows:
+        zero = (torch.rand(-(-M // 8), device=dev) < 0.5).repeat_interleave(8)[:M]
+        denc[zero | (torch.rand(M, device=dev) < 0.4)] = 0.0
+        nz = torch.nn.functional.pad((denc != 0).any(1).to(torch.int64), (0, -M % 32)).view(-1, 32)
+        w = (nz << torch.arange(32, device=dev)[None]).sum(1)
+        bits = torch.where(w >= 2**31, w - 2**32, w).to(torch.int32)
+        extra, entry = (bits.data_ptr(),), "anr_hashgrid_bwd_rows"
     lib = _lib.load()
     s = _lib.stream(dev)
     grads = {}
@@ -58,9 +74,8 @@ def main():
                 timer.__enter__()
             if it == args.iters + 1:
                 grad.zero_()
-            _lib.call("anr_hashgrid_bwd", ctypes.byref(desc), x.data_ptr(), 3, M,
-                      denc.data_ptr(), _lib.F32, 32, grad.data_ptr(), s,
-                      tag=f"hash_bwd_m{mode}")
+            _lib.call(entry, ctypes.byref(desc), x.data_ptr(), D, M, denc.data_ptr(), gdt, 32,
+                      grad.data_ptr(), *extra, s, tag=f"hash_bwd_m{mode}")
         timer.__exit__(None, None, None)
         torch.cuda.synchronize()
         lib.anr_hashgrid_force_v1(prev)

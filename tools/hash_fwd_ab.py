@@ -1,11 +1,10 @@
 """A/B of the hash-grid forward generations at bench size (profiling aid).
 
-    python tools/hash_fwd_ab.py [--modes 1,0] [--iters 10] [--log2t 19]
+    python tools/hash_fwd_ab.py [--modes 1,0] [--iters 10] [--log2t 19] [--table f32]
 
 Bench coordinates (synthetic HARP2 scene -> fused sampler, 8192 rays x 1024 samples), f16
 table, f16 output; modes as anr_hashgrid_force_v1 (0 = v6, 1 = v1), or "p" for
-anr_hashgrid_fwd_planar (v8, level-pair planes, converted back to rows for the check;
-removed from the library after profiles/r03_hash_levels.md §3).
+anr_hashgrid_fwd_planes (v9, level-quad planes, converted back to rows for the check).
 Every mode's output is compared bit for bit with mode 1's (or mode 0's). Prints the HIP-event average per mode. (The r02 log's
 mode 7, a level-major-plane experiment, was removed from the library after measuring it.)
 """
@@ -34,6 +33,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--modes", default="1,0")
     ap.add_argument("--views", type=int, default=8)
+    ap.add_argument("--table", choices=["f16", "f32"], default="f16")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -50,24 +50,27 @@ def main():
     x = coords.reshape(M, 3).contiguous()
     desc = _lib.hashgrid_desc(3, 16, 2, 16, 1.3819, args.log2t)
     table = ((torch.rand(desc.n_params, device=dev) * 2 - 1) * 1e-2).half()
+    tdt = _lib.F16
+    if args.table == "f32":
+        table, tdt = table.float(), _lib.F32
     lib = _lib.load()
     s = _lib.stream(dev)
     outs = {}
     for mode in [m if m == "p" else int(m) for m in args.modes.split(",")]:
         enc = torch.empty(M, 32, device=dev, dtype=torch.float16)
-        planes = torch.empty(8, M, 4, device=dev, dtype=torch.float16)
+        planes = torch.empty(4, M, 8, device=dev, dtype=torch.float16)
         prev = lib.anr_hashgrid_force_v1(0 if mode == "p" else mode)
         timer = _lib.KernelTimer()
         for it in range(args.iters + 2):
             if it == 2:
                 timer.__enter__()
             if mode == "p":
-                _lib.call("anr_hashgrid_fwd_planar", ctypes.byref(desc), x.data_ptr(), 3, M,
-                          table.data_ptr(), _lib.F16, planes.data_ptr(), _lib.F16, s,
-                          tag="hash_fwd_planar")
+                _lib.call("anr_hashgrid_fwd_planes", ctypes.byref(desc), x.data_ptr(), 3, M,
+                          table.data_ptr(), tdt, planes.data_ptr(), 8 * M, s,
+                          tag="hash_fwd_planes")
             else:
                 _lib.call("anr_hashgrid_fwd", ctypes.byref(desc), x.data_ptr(), 3, M,
-                          table.data_ptr(), _lib.F16, enc.data_ptr(), _lib.F16, 32, s,
+                          table.data_ptr(), tdt, enc.data_ptr(), _lib.F16, 32, s,
                           tag=f"hash_fwd_m{mode}")
         timer.__exit__(None, None, None)
         torch.cuda.synchronize()

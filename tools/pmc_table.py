@@ -14,8 +14,8 @@ import os
 import sys
 
 KERNELS = {"hash_fwd": "hashgrid_fwd_planes_kernel<",
-           "hash_bwd": "hashgrid_bwd_v2_kernel<3, __half, 3, 32, false, 6, true>",
-           "hash_bwd_build": "hashgrid_bwd_v2_kernel<3, float, 3, 32",
+           "hash_bwd": "hashgrid_bwd_v2_kernel<3, __half, anr::RowBitsWalk>",
+           "hash_bwd_build": "hashgrid_bwd_v2_kernel<3, float, anr::DenseWalk<3, 32>",
            "field_fwd": "field::fwd_kernel<64, 2",
            "hash_field_fwd": "hf_fwd_kernel<64, 2",
            "field_bwd": "field::bwd_rt_kernel<64, 2, false, 1, anr::field::PosPass<",

@@ -47,9 +47,9 @@ TAGS = {  # prefixes: one instantiation of each per bench run (width / dtype fol
     "hash_fwd_v1": "hashgrid_fwd_kernel<3,",
     # reference numerics (the headline): the row-bit walker over f16 rows (r06); the build
     # numerics' dense f32 walker beside it (bench.py's alt_numerics leg)
-    "hash_bwd": "hashgrid_bwd_v2_kernel<3, __half, 3, 32, false, 6, true>",
-    "hash_bwd_build": "hashgrid_bwd_v2_kernel<3, float, 3, 32, false, 6, false>",
-    "hash_bwd_rtstride": "hashgrid_bwd_v2_kernel<3, float, 0, 0>",
+    "hash_bwd": "hashgrid_bwd_v2_kernel<3, __half, anr::RowBitsWalk>",
+    "hash_bwd_build": "hashgrid_bwd_v2_kernel<3, float, anr::DenseWalk<3, 32>",
+    "hash_bwd_rtstride": "hashgrid_bwd_v2_kernel<3, float, anr::DenseWalk<0, 0>",
     # last argument: f16 outputs (reference numerics; false with ANR_REF_F16_IO=0 and in the
     # build numerics' leg of the same run). A tuple: every part must occur in the name
     "field_fwd": ("field::fwd_kernel<", ", true>(anr::field::Args)"),

@@ -347,6 +347,20 @@ _SIGNATURES = {
         [POINTER(SparseVolumeDesc), c_int32, _P, c_int64, c_int64, c_int64, POINTER(VolumeParams),
          _P, _P, _P],
     ),
+    "anr_volume_light": (
+        c_int32, [_P, c_int64, c_int64, c_int64, POINTER(VolumeParams), _P, _P]),
+    "anr_volume_render_lit": (
+        c_int32,
+        [_P, _P, c_int64, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(VolumeParams),
+         _P, _P],
+    ),
+    "anr_sparse_volume_light": (
+        c_int32, [POINTER(SparseVolumeDesc), c_int32, POINTER(VolumeParams), _P, _P]),
+    "anr_sparse_volume_render_lit": (
+        c_int32,
+        [POINTER(SparseVolumeDesc), _P, c_int32, _P, c_int64, c_int64, c_int64,
+         POINTER(VolumeParams), _P, _P, _P],
+    ),
     "anr_composite_force_generic": (c_int32, [c_int32]),
     "anr_composite_fwd": (
         c_int32,

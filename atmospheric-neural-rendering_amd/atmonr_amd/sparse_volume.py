@@ -31,8 +31,8 @@ import torch
 
 from . import _lib
 from ._lib import ANRError
-from .video import (DEFAULT_HFOV, VolumeRenderSettings, look_at_camera, stitch_frames,
-                    write_ppm)
+from .video import (DEFAULT_HFOV, LightVolume, VolumeRenderSettings, check_shadows, light_key,
+                    look_at_camera, stitch_frames, write_ppm)
 
 
 class SparseVolume:
@@ -45,6 +45,7 @@ class SparseVolume:
         self.lo, self.ext, self.row_pitch = tuple(lo), tuple(ext), int(row_pitch)
         self.cells, self.values, self.coarse = cells, values, coarse
         self.density_scale = float(density_scale)
+        self._light = None  # the last light volume built: (key, skip) and the LightVolume
 
     def __len__(self) -> int:
         return int(self.values.shape[0])
@@ -151,6 +152,24 @@ class SparseVolume:
                                torch.from_numpy(np.ascontiguousarray(sigma[:, band])).to(device),
                                density_scale)
 
+    def light(self, settings: VolumeRenderSettings | None = None,
+              skip: bool = True) -> LightVolume:
+        """``anr_sparse_volume_light``: the :class:`LightVolume` of this volume under
+        ``settings`` (default :func:`global_settings`), ``tau`` (n,) f32 in value order (as
+        many bytes again as ``values``). The volume is immutable, so the last one built is
+        kept and returned again for settings with the same :func:`light_key`; other settings
+        build another. ``skip=False`` switches the brick level off (same values)."""
+        settings = global_settings(self) if settings is None else settings
+        key = light_key(settings)
+        if self._light is not None and self._light[0] == key:
+            return self._light[1]
+        tau = torch.empty_like(self.values)
+        with torch.cuda.device(self.device):
+            _lib.call("anr_sparse_volume_light", ctypes.byref(self.desc(skip)), int(skip),
+                      settings.params(), _lib.ptr(tau), _lib.stream(self.device))
+        self._light = (key, LightVolume(tau, key))
+        return self._light[1]
+
     def sample(self, positions: torch.Tensor, skip: bool = True) -> torch.Tensor:
         """``D`` at (P, 3) f32 box-relative positions (``anr_sparse_volume_sample``): (P,)
         f32. ``skip=False`` looks every corner up instead of asking the brick level first;
@@ -193,14 +212,20 @@ def voxel_edge(grid_res: float, grid_scale: float | None = None) -> float:
 def render_sparse_volume(volume: SparseVolume, cameras: torch.Tensor, width: int = 640,
                          height: int = 480, settings: VolumeRenderSettings | None = None,
                          max_bytes: int = 1 << 28, skip: bool = True,
-                         counters: torch.Tensor | None = None) -> torch.Tensor:
+                         counters: torch.Tensor | None = None, shadows: str = "marched",
+                         light: LightVolume | None = None) -> torch.Tensor:
     """(F, height, width, 4) f32 RGBA on the device: ``anr_sparse_volume_render`` of
     ``volume`` from the (F, 12) f32 box-relative ``cameras``; ``settings`` default to
     :func:`global_settings`. Mirrors ``render_volume``: the frames go to the kernel in chunks
     whose output stays under ``max_bytes`` (at least one frame per launch), and frames are
     independent, so the chunking does not change a bit. ``skip=False`` switches the brick
     level off (same output). ``counters``: a zeroed (2,) int64 GPU tensor that receives the
-    samples taken inside the box and those of them the brick level answered."""
+    samples taken inside the box and those of them the brick level answered.
+
+    ``shadows="light_volume"``: ``anr_sparse_volume_render_lit`` with ``light``, by default
+    ``volume.light(settings)`` (built once, then kept by the volume); one built for other
+    settings raises ANRError. An unknown ``shadows`` raises ValueError."""
+    lit = check_shadows(shadows)
     if not isinstance(volume, SparseVolume):
         raise ANRError("render_sparse_volume needs a SparseVolume")
     settings = global_settings(volume) if settings is None else settings
@@ -221,9 +246,19 @@ def render_sparse_volume(volume: SparseVolume, cameras: torch.Tensor, width: int
         return out
     params, desc = settings.params(), volume.desc(skip)
     chunk = max(1, int(max_bytes) // (height * width * 16))
+    if lit:
+        light = volume.light(settings, skip) if light is None else light
+        light.check(settings, volume.values.shape, volume.device)
+        tau = light.tau.contiguous()
     with torch.cuda.device(volume.device):
         for f0 in range(0, F, chunk):
             n = min(chunk, F - f0)
+            if lit:
+                _lib.call("anr_sparse_volume_render_lit", ctypes.byref(desc), _lib.ptr(tau),
+                          int(skip), _lib.ptr(cameras[f0:f0 + n]), n, height, width, params,
+                          _lib.ptr(out[f0:f0 + n]), _lib.ptr(counters),
+                          _lib.stream(volume.device))
+                continue
             _lib.call("anr_sparse_volume_render", ctypes.byref(desc), int(skip),
                       _lib.ptr(cameras[f0:f0 + n]), n, height, width, params,
                       _lib.ptr(out[f0:f0 + n]), _lib.ptr(counters), _lib.stream(volume.device))
@@ -285,27 +320,33 @@ def make_global_video(volume, out_dir, video_path=None, sigma=None, band: int = 
                       grid_scale: float | None = None, width: int = 640, height: int = 480,
                       duration: float = 10.0, frame_rate: int = 60,
                       settings: VolumeRenderSettings | None = None,
-                      device: torch.device | str = "cuda", max_bytes: int = 1 << 28) -> dict:
+                      device: torch.device | str = "cuda", max_bytes: int = 1 << 28,
+                      shadows: str = "marched", light: LightVolume | None = None) -> dict:
     """The orbit video of a global-grid extract. ``volume``: a :class:`SparseVolume`, or the
     voxels (``voxels.npy`` or an (n, 3) array) with ``sigma`` (``sigma.npy`` or (n, bands)),
     which go through :meth:`SparseVolume.from_files` with ``band``, ``density_scale``,
     ``grid_res`` and ``grid_scale``. One frame per camera of :func:`global_orbit_cameras` is
     written to ``out_dir`` as ``%06d.ppm`` and, with a ``video_path`` and an ``ffmpeg`` binary
     already on PATH, stitched by the script's ffmpeg call. Returns what ``make_video``
-    returns, ``"shape"`` being the box extents."""
+    returns, ``"shape"`` being the box extents. ``shadows="light_volume"``: the light volume
+    is built once for the whole video (``volume.light``), or ``light`` is taken, if it was
+    built for these settings."""
+    lit = check_shadows(shadows)
     if not isinstance(volume, SparseVolume):
         if sigma is None:
             raise ANRError("make_global_video: voxels need their sigma")
         volume = SparseVolume.from_files(volume, sigma, band, density_scale, grid_res,
                                          grid_scale, device)
     cameras = global_orbit_cameras(volume, duration, frame_rate, width, height)
+    if lit and light is None:
+        light = volume.light(settings)
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     frames = []
     chunk = max(1, int(max_bytes) // max(1, height * width * 16))
     for f0 in range(0, cameras.shape[0], chunk):
         rgba = render_sparse_volume(volume, cameras[f0:f0 + chunk], width, height, settings,
-                                    max_bytes)
+                                    max_bytes, shadows=shadows, light=light if lit else None)
         for k, img in enumerate(rgba.cpu().numpy()):
             frames.append(str(out_dir / f"{f0 + k:06d}.ppm"))
             write_ppm(frames[-1], img)

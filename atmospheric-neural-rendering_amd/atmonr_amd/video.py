@@ -7,6 +7,14 @@ GPU by ``anr_volume_render`` (csrc/volume_render.hip; the arithmetic is defined 
 include/anr.h and restated in tests/volume_checks.py). The defaults are vdb_render's and the
 script's; parity with vdb_render: unpinned. No VDB file is written, and nothing is fetched:
 ffmpeg runs only if a binary is already on PATH, otherwise the frames stay as PPM files.
+
+Shadows: ``shadows="marched"`` (the default) casts a shadow march at every primary sample.
+``shadows="light_volume"`` is a second, opt-in mode: the light does not move during an orbit,
+so the shadow optical depth of every voxel is summed once (:func:`light_volume`,
+``anr_volume_light``) and interpolated at each primary sample (``anr_volume_render_lit``). An
+interpolated shadow is not a marched one: the mode has its own definition in include/anr.h and
+its own yardstick (tests/light_volume_checks.py); the alpha channel is the marched mode's bit
+for bit, the colours differ. Parity with vdb_render: unpinned.
 """
 
 from __future__ import annotations
@@ -53,6 +61,67 @@ class VolumeRenderSettings:
         p.primary_step, p.shadow_step = float(self.primary_step), float(self.shadow_step)
         p.light_gain, p.cutoff = float(self.light_gain), float(self.cutoff)
         return p
+
+
+SHADOWS = ("marched", "light_volume")
+
+
+def check_shadows(shadows) -> bool:
+    """True for the light-volume mode; ValueError for a name that is neither mode."""
+    if shadows not in SHADOWS:
+        raise ValueError(f"shadows must be one of {SHADOWS}, got {shadows!r}")
+    return shadows == "light_volume"
+
+
+def light_key(settings: VolumeRenderSettings) -> tuple:
+    """What a light volume depends on besides the density: light_dir, shadow_step, light_gain
+    and cutoff, as the f32 values the kernel receives."""
+    vals = (*settings.light_dir, settings.shadow_step, settings.light_gain, settings.cutoff)
+    return tuple(float(np.float32(v)) for v in vals)
+
+
+class LightVolume:
+    """The shadow optical depth ``tau`` of every voxel of one volume under one light: a tensor
+    of the cube's shape (dense) or of the values' (sparse), with the ``key``
+    (:func:`light_key`) of the settings it was built for. Valid only for the density it was
+    built from; the renders refuse it under settings with another key."""
+
+    def __init__(self, tau: torch.Tensor, key: tuple) -> None:
+        self.tau, self.key = tau, tuple(key)
+
+    def check(self, settings: VolumeRenderSettings, shape, device) -> None:
+        if self.key != light_key(settings):
+            raise ANRError("the light volume was built for other settings (light_dir, "
+                           f"shadow_step, light_gain, cutoff) = {self.key}, the render asks "
+                           f"for {light_key(settings)}")
+        if tuple(self.tau.shape) != tuple(shape) or self.tau.device != device:
+            raise ANRError(f"the light volume has shape {tuple(self.tau.shape)} on "
+                           f"{self.tau.device}, the volume {tuple(shape)} on {device}")
+
+
+def _check_density(density: torch.Tensor, who: str) -> None:
+    if not density.is_cuda:
+        raise ANRError(f"{who} needs GPU tensors (got a CPU tensor)")
+    if density.dim() != 3 or density.dtype != torch.float32:
+        raise ANRError(f"density must be (nx, ny, nz) float32, got {tuple(density.shape)} "
+                       f"{density.dtype}")
+
+
+def light_volume(density: torch.Tensor,
+                 settings: VolumeRenderSettings | None = None) -> LightVolume:
+    """``anr_volume_light`` of the (nx, ny, nz) f32 cube ``density``: the :class:`LightVolume`
+    that ``render_volume(..., shadows="light_volume", light=...)`` takes. Build it once per
+    video; it holds as long as the density and the settings' light_dir, shadow_step,
+    light_gain and cutoff do. CPU tensors raise ANRError."""
+    settings = VolumeRenderSettings() if settings is None else settings
+    _check_density(density, "light_volume")
+    density = density.contiguous()
+    tau = torch.empty_like(density)
+    nx, ny, nz = density.shape
+    with torch.cuda.device(density.device):
+        _lib.call("anr_volume_light", _lib.ptr(density), nx, ny, nz, settings.params(),
+                  _lib.ptr(tau), _lib.stream(density.device))
+    return LightVolume(tau, light_key(settings))
 
 
 def volume_from_extract(extinction, band: int = 2, scene_scale: float = 1000.0) -> np.ndarray:
@@ -124,11 +193,18 @@ def orbit_cameras(shape, duration: float = 10.0, frame_rate: int = 60, width: in
 
 def render_volume(density: torch.Tensor, cameras: torch.Tensor, width: int = 640,
                   height: int = 480, settings: VolumeRenderSettings | None = None,
-                  max_bytes: int = 1 << 28) -> torch.Tensor:
+                  max_bytes: int = 1 << 28, shadows: str = "marched",
+                  light: LightVolume | None = None) -> torch.Tensor:
     """(F, height, width, 4) f32 RGBA on the device: ``anr_volume_render`` of the (nx, ny, nz)
     f32 cube ``density`` from the (F, 12) f32 ``cameras``. The frames go to the kernel in
     chunks whose output stays under ``max_bytes`` (at least one frame per launch); frames are
-    independent, so the chunking does not change a bit. CPU tensors raise ANRError."""
+    independent, so the chunking does not change a bit. CPU tensors raise ANRError.
+
+    ``shadows="light_volume"``: ``anr_volume_render_lit`` with ``light``, a
+    :func:`light_volume` of this density under these settings (built here, for this call
+    alone, when None; one built for other settings raises ANRError). An unknown ``shadows``
+    raises ValueError."""
+    lit = check_shadows(shadows)
     settings = VolumeRenderSettings() if settings is None else settings
     if not (density.is_cuda and cameras.is_cuda):
         raise ANRError("render_volume needs GPU tensors (got a CPU tensor)")
@@ -148,12 +224,21 @@ def render_volume(density: torch.Tensor, cameras: torch.Tensor, width: int = 640
     params = settings.params()
     chunk = max(1, int(max_bytes) // (height * width * 16))
     nx, ny, nz = density.shape
+    if lit:
+        light = light_volume(density, settings) if light is None else light
+        light.check(settings, density.shape, density.device)
+        tau = light.tau.contiguous()
     with torch.cuda.device(density.device):
         for f0 in range(0, F, chunk):
             n = min(chunk, F - f0)
-            _lib.call("anr_volume_render", _lib.ptr(density), nx, ny, nz,
-                      _lib.ptr(cameras[f0:f0 + n]), n, height, width, params,
-                      _lib.ptr(out[f0:f0 + n]), _lib.stream(density.device))
+            if lit:
+                _lib.call("anr_volume_render_lit", _lib.ptr(density), _lib.ptr(tau), nx, ny, nz,
+                          _lib.ptr(cameras[f0:f0 + n]), n, height, width, params,
+                          _lib.ptr(out[f0:f0 + n]), _lib.stream(density.device))
+            else:
+                _lib.call("anr_volume_render", _lib.ptr(density), nx, ny, nz,
+                          _lib.ptr(cameras[f0:f0 + n]), n, height, width, params,
+                          _lib.ptr(out[f0:f0 + n]), _lib.stream(density.device))
     return out
 
 
@@ -210,15 +295,20 @@ def stitch_frames(result: dict, out_dir, video_path, frame_rate: int, width: int
 def make_video(extract, out_dir, video_path=None, band: int = 2, scene_scale: float = 1000.0,
                width: int = 640, height: int = 480, duration: float = 10.0,
                frame_rate: int = 60, settings: VolumeRenderSettings | None = None,
-               device: torch.device | str = "cuda", max_bytes: int = 1 << 28) -> dict:
+               device: torch.device | str = "cuda", max_bytes: int = 1 << 28,
+               shadows: str = "marched", light: LightVolume | None = None) -> dict:
     """scripts/make_video.py:142-199: the extract's cube, an orbit around it, one frame per
     camera written to ``out_dir`` as ``%06d.ppm`` (the script's temp-frame naming), and, with
     a ``video_path`` and an ``ffmpeg`` binary already on PATH, the script's ffmpeg call.
     ``extract``: what volume_from_extract takes. Returns ``{"frames": [paths], "shape": cube
     shape, "video": path or None, "ffmpeg": what happened}``; without ffmpeg the frames stay
-    and ``"ffmpeg"`` says so."""
+    and ``"ffmpeg"`` says so. ``shadows="light_volume"``: the light volume is built once for
+    the whole video (or ``light`` is taken, if it was built for these settings)."""
+    lit = check_shadows(shadows)
     cube = volume_from_extract(extract, band=band, scene_scale=scene_scale)
     density = torch.from_numpy(cube).to(device)
+    if lit and light is None:
+        light = light_volume(density, settings)
     cameras = orbit_cameras(cube.shape, duration, frame_rate, width, height, device=device)
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -226,7 +316,8 @@ def make_video(extract, out_dir, video_path=None, band: int = 2, scene_scale: fl
     per_frame = max(1, height * width * 16)
     chunk = max(1, int(max_bytes) // per_frame)
     for f0 in range(0, cameras.shape[0], chunk):
-        rgba = render_volume(density, cameras[f0:f0 + chunk], width, height, settings, max_bytes)
+        rgba = render_volume(density, cameras[f0:f0 + chunk], width, height, settings, max_bytes,
+                             shadows=shadows, light=light if lit else None)
         for k, img in enumerate(rgba.cpu().numpy()):
             frames.append(str(out_dir / f"{f0 + k:06d}.ppm"))
             write_ppm(frames[-1], img)

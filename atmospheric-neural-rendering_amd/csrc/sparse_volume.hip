@@ -116,6 +116,133 @@ struct SparseVol {
   }
 };
 
+// The volume with its light volume: tau in value order, so the rank that finds a corner's
+// density finds its tau.
+template <bool kSkip, bool kStats>
+struct SparseVolLit : SparseVol<kSkip, kStats> {
+  using Base = SparseVol<kSkip, kStats>;
+  const float* tau;
+
+  __device__ __forceinline__ SparseVolLit(const SpvGeom& g, const float* t) : Base(g), tau(t) {}
+
+  // The value and its index in values (and tau) of bit b of cell c; 0 and -1 where absent.
+  __device__ __forceinline__ void cell_at(uint2 c, int b, float* v, int32_t* at) const {
+    *v = 0.0f;
+    *at = -1;
+    if (!((c.x >> b) & 1u)) return;
+    *at = static_cast<int32_t>(c.y + __popc(c.x & ((1u << b) - 1u)));
+    *v = this->values[*at];
+  }
+
+  // row_pair, with the indices.
+  __device__ __forceinline__ void row_pair_at(int i, int jj, int kk, float* a, float* b,
+                                              int32_t* ia, int32_t* ib) const {
+    *a = 0.0f;
+    *b = 0.0f;
+    *ia = -1;
+    *ib = -1;
+    if (jj < 0 || kk < 0 || jj >= this->ny || kk >= this->nz) return;
+    const int32_t base = (kk * this->ny + jj) * this->pitch_words;
+    const int i1 = i + 1;
+    int w0 = -1;
+    uint2 c0 = make_uint2(0u, 0u);
+    if (i >= 0) {
+      w0 = i >> 5;
+      c0 = this->cells[base + w0];
+      cell_at(c0, i & 31, a, ia);
+    }
+    if (i1 < this->nx) {
+      const int w1 = i1 >> 5;
+      const uint2 c1 = w1 == w0 ? c0 : this->cells[base + w1];
+      cell_at(c1, i1 & 31, b, ib);
+    }
+  }
+
+  // sample(p), and in *tau_hat, where that is >= cutoff, the mean of tau over the corners
+  // with density > 0 (vol_lit_corners). A dead brick has no such corner.
+  __device__ __forceinline__ float lit_sample(float px, float py, float pz, float cutoff,
+                                              float* tau_hat) {
+    const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+    if (!(fx >= -1.0f && fy >= -1.0f && fz >= -1.0f && fx <= static_cast<float>(this->nx - 1) &&
+          fy <= static_cast<float>(this->ny - 1) && fz <= static_cast<float>(this->nz - 1)))
+      return 0.0f;
+    const float wx = px - fx, wy = py - fy, wz = pz - fz;
+    const int i = static_cast<int>(fx), j = static_cast<int>(fy), k = static_cast<int>(fz);
+    if (kStats) ++this->n_samples;
+    if (kSkip) {
+      const int32_t brick =
+          (((k + 1) >> kSpvBrickLog2) * this->nby + ((j + 1) >> kSpvBrickLog2)) * this->nbx +
+          ((i + 1) >> kSpvBrickLog2);
+      if (!((this->coarse[brick >> 5] >> (brick & 31)) & 1u)) {
+        if (kStats) ++this->n_skipped;
+        return 0.0f;
+      }
+    }
+    // corners in x-outer, z-inner order
+    float v[8];
+    int32_t at[8];
+    row_pair_at(i, j, k, &v[0], &v[4], &at[0], &at[4]);
+    row_pair_at(i, j, k + 1, &v[1], &v[5], &at[1], &at[5]);
+    row_pair_at(i, j + 1, k, &v[2], &v[6], &at[2], &at[6]);
+    row_pair_at(i, j + 1, k + 1, &v[3], &v[7], &at[3], &at[7]);
+    const float dens = vol_trilerp(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], wx, wy, wz);
+    if (dens < cutoff) return dens;
+    float tv[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) tv[c] = v[c] > 0.0f ? tau[at[c]] : 0.0f;
+    *tau_hat = vol_lit_corners(v, tv, wx, wy, wz);
+    return dens;
+  }
+};
+
+template <bool kSkip, bool kStats>
+__global__ void __launch_bounds__(kVolThreads) sparse_volume_render_lit_kernel(
+    SpvGeom g, const float* __restrict__ tau, const anr_camera* __restrict__ cams, int32_t H,
+    int32_t W, int32_t tiles_x, int32_t tiles_y, VolMarch m, float* __restrict__ rgba,
+    unsigned long long* __restrict__ counters) {
+  SparseVolLit<kSkip, kStats> vol(g, tau);
+  vol_march_pixel<true>(vol, cams, H, W, tiles_x, tiles_y, m, rgba);
+  if (kStats) {
+    if (vol.n_samples) atomicAdd(counters + 0, vol.n_samples);
+    if (vol.n_skipped) atomicAdd(counters + 1, vol.n_skipped);
+  }
+}
+
+// One thread per value, in value order, so the 64 lanes of a wavefront are 64 present voxels
+// that follow each other in the bitmap and every lane walks. The thread finds its voxel from
+// the ranks: the last word whose rank is <= r holds it (an empty word shares its rank with
+// the next word, so it is never the last), as the (r - rank)-th set bit. About 27 dependent
+// 8-byte loads at the default grid, against a walk of hundreds of samples.
+template <bool kSkip>
+__global__ void __launch_bounds__(kSpvThreads) sparse_volume_light_kernel(
+    SpvGeom g, int32_t n_words, int32_t n_values, VolMarch m, float* __restrict__ tau) {
+  const int64_t r64 = static_cast<int64_t>(blockIdx.x) * kSpvThreads + threadIdx.x;
+  if (r64 >= n_values) return;
+  const uint32_t r = static_cast<uint32_t>(r64);
+  int32_t lo = 0, hi = n_words - 1;  // the answer lies in [lo, hi]; rank of word 0 is 0
+  while (lo < hi) {
+    const int32_t mid = lo + (hi - lo + 1) / 2;
+    if (g.cells[mid].y <= r)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const uint2 c = g.cells[lo];
+  float t = 0.0f;
+  // ranks that disagree with the bitmap find no bit: the voxel keeps 0
+  if (c.y <= r && r - c.y < static_cast<uint32_t>(__popc(c.x)) && g.values[r] > 0.0f) {
+    uint32_t bits = c.x;
+    for (uint32_t q = r - c.y; q > 0; --q) bits &= bits - 1u;
+    const int32_t row = lo / g.pitch_words;
+    const int32_t k = row / g.ny;
+    const float p[3] = {static_cast<float>((lo - row * g.pitch_words) * 32 + (__ffs(bits) - 1)),
+                        static_cast<float>(row - k * g.ny), static_cast<float>(k)};
+    SparseVol<kSkip, false> vol(g);
+    t = vol_light_tau(vol, p, m);
+  }
+  tau[r] = t;
+}
+
 template <bool kSkip, bool kStats>
 __global__ void __launch_bounds__(kVolThreads) sparse_volume_render_kernel(
     SpvGeom g, const anr_camera* __restrict__ cams, int32_t H, int32_t W, int32_t tiles_x,
@@ -373,5 +500,72 @@ extern "C" int anr_sparse_volume_render(const anr_sparse_volume* volume, int32_t
     ANR_SPV_LAUNCH(false, false);
 #undef ANR_SPV_LAUNCH
   ANR_CHECK_LAUNCH("anr_sparse_volume_render");
+  return ANR_OK;
+}
+
+extern "C" int anr_sparse_volume_light(const anr_sparse_volume* volume, int32_t skip,
+                                       const anr_volume_params* params, float* tau,
+                                       anr_stream_t stream) {
+  using namespace anr;
+  ANR_CHECK_ARG(params != nullptr, "anr_sparse_volume_light: null pointer (params)");
+  SpvGeom g;
+  const char* why = spv_geom(volume, skip, &g);
+  ANR_CHECK_ARG(why == nullptr, "anr_sparse_volume_light: %s", why);
+  VolMarch m;
+  int64_t tiles_x = 0, tiles_y = 0;
+  bool empty = true;
+  // the plan of a 1 x 1 image: its refusals and the walk's integer bound
+  const int rc = vol_plan("anr_sparse_volume_light", g.nx, g.ny, g.nz, 1, 1, 1, params, &m,
+                          &tiles_x, &tiles_y, &empty);
+  if (rc != ANR_OK) return rc;
+  ANR_CHECK_ARG(g.cells && g.values && (g.coarse || !skip) && tau,
+                "anr_sparse_volume_light: null pointer");
+  const int32_t n_values = static_cast<int32_t>(volume->n_values);
+  const int32_t n_words = g.pitch_words * g.ny * g.nz;  // < 2^31: spv_box
+  const dim3 grid(static_cast<unsigned>(ceil_div(volume->n_values, kSpvThreads)));
+  if (skip)
+    hipLaunchKernelGGL(sparse_volume_light_kernel<true>, grid, dim3(kSpvThreads), 0,
+                       as_stream(stream), g, n_words, n_values, m, tau);
+  else
+    hipLaunchKernelGGL(sparse_volume_light_kernel<false>, grid, dim3(kSpvThreads), 0,
+                       as_stream(stream), g, n_words, n_values, m, tau);
+  ANR_CHECK_LAUNCH("anr_sparse_volume_light");
+  return ANR_OK;
+}
+
+extern "C" int anr_sparse_volume_render_lit(const anr_sparse_volume* volume, const float* tau,
+                                            int32_t skip, const anr_camera* cameras, int64_t F,
+                                            int64_t H, int64_t W, const anr_volume_params* params,
+                                            float* rgba, int64_t* counters, anr_stream_t stream) {
+  using namespace anr;
+  ANR_CHECK_ARG(params != nullptr, "anr_sparse_volume_render_lit: null pointer (params)");
+  SpvGeom g;
+  const char* why = spv_geom(volume, skip, &g);
+  ANR_CHECK_ARG(why == nullptr, "anr_sparse_volume_render_lit: %s", why);
+  VolMarch m;
+  int64_t tiles_x = 0, tiles_y = 0;
+  bool empty = true;
+  const int rc = vol_plan("anr_sparse_volume_render_lit", g.nx, g.ny, g.nz, F, H, W, params, &m,
+                          &tiles_x, &tiles_y, &empty);
+  if (rc != ANR_OK || empty) return rc;
+  ANR_CHECK_ARG(g.cells && g.values && (g.coarse || !skip) && tau && cameras && rgba,
+                "anr_sparse_volume_render_lit: null pointer");
+  const dim3 grid(static_cast<unsigned>(tiles_x * tiles_y * F)), block(kVolThreads);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+  const int32_t h = static_cast<int32_t>(H), w = static_cast<int32_t>(W);
+  const int32_t tx = static_cast<int32_t>(tiles_x), ty = static_cast<int32_t>(tiles_y);
+#define ANR_SPV_LAUNCH(S, C)                                                                  \
+  hipLaunchKernelGGL((sparse_volume_render_lit_kernel<S, C>), grid, block, 0, as_stream(stream), \
+                     g, tau, cameras, h, w, tx, ty, m, rgba, cnt)
+  if (skip && cnt)
+    ANR_SPV_LAUNCH(true, true);
+  else if (skip)
+    ANR_SPV_LAUNCH(true, false);
+  else if (cnt)
+    ANR_SPV_LAUNCH(false, true);
+  else
+    ANR_SPV_LAUNCH(false, false);
+#undef ANR_SPV_LAUNCH
+  ANR_CHECK_LAUNCH("anr_sparse_volume_render_lit");
   return ANR_OK;
 }

@@ -6,6 +6,15 @@
 // and nothing else of it is used here, so both volumes take the same steps at the same t, and
 // only where the eight values of a sample come from differs.
 //
+// Light volume (the second, opt-in shadow mode; include/anr.h "Light volume"): the light does
+// not move during an orbit, so the shadow optical depth tau of every voxel is summed once
+// (vol_light_tau: the shadow loop below without its early termination) and the lit march
+// (vol_march_pixel<true>) interpolates it where the marched mode casts a shadow ray. An
+// accessor of the lit march also has
+//   float lit_sample(float px, float py, float pz, float cutoff, float* tau_hat);
+// which returns sample(p) and, where that is >= cutoff, the weighted mean of tau over the
+// corners with density > 0 (vol_lit_corners), from the same eight corner loads.
+//
 // Pixels: a 256-thread block renders a 16 x 16 pixel tile of one frame, each of its four
 // wavefronts an 8 x 8 sub-tile, so the 64 rays of a wavefront stay close together: their
 // gathers share cache lines and they leave the march at about the same step. One lane marches
@@ -73,9 +82,49 @@ __device__ __forceinline__ bool vol_clip(int32_t nx, int32_t ny, int32_t nz, con
   return ok && tn <= tf && tf >= 0.0f;
 }
 
-// One pixel of one frame (block -> (frame, tile); thread -> pixel of the tile, 8 x 8 per
-// wavefront). `vol` is the thread's own copy of the accessor.
+// tau of the voxel at p: the shadow loop of vol_march_pixel from p (the light ray clipped to
+// the box, s = shadow_step, 2 shadow_step, ... <= s1, samples below cutoff skipped, the
+// integer bound kept) as a plain sum of optical depths: never ended early, and the same for
+// every channel. Shared by the dense and the sparse light build.
 template <typename Vol>
+__device__ __forceinline__ float vol_light_tau(Vol& vol, const float p[3], const VolMarch& m) {
+  float tau = 0.0f;
+  float s0, s1;
+  if (!vol_clip(vol.nx, vol.ny, vol.nz, p, m.light, &s0, &s1)) return tau;
+  for (int32_t q = 1; q <= m.max_shadow; ++q) {
+    const float s = static_cast<float>(q) * m.shadow_step;
+    if (!(s <= s1)) break;
+    const float ds = vol.sample(p[0] + s * m.light[0], p[1] + s * m.light[1],
+                                p[2] + s * m.light[2]);
+    if (ds < m.cutoff) continue;
+    tau += ds * m.shadow_step / (1.0f + s * m.light_gain);
+  }
+  return tau;
+}
+
+// tau_hat of a lit sample: over the eight corners v[x][y][z], x outermost, z innermost, the low
+// corner first, ww = (wx_a * wy_b) * wz_c; a corner takes part if its density is > 0 (absent
+// and outside corners arrive here as 0), and tau_hat = sum ww tau / sum ww, 0 with no corner.
+__device__ __forceinline__ float vol_lit_corners(const float v[8], const float tau[8], float wx,
+                                                 float wy, float wz) {
+  const float ax[2] = {1.0f - wx, wx}, ay[2] = {1.0f - wy, wy}, az[2] = {1.0f - wz, wz};
+  float num = 0.0f, den = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const float ww = (ax[c >> 2] * ay[(c >> 1) & 1]) * az[c & 1];
+    if (v[c] > 0.0f) {
+      num += ww * tau[c];
+      den += ww;
+    }
+  }
+  return den > 0.0f ? num / den : 0.0f;
+}
+
+// One pixel of one frame (block -> (frame, tile); thread -> pixel of the tile, 8 x 8 per
+// wavefront). `vol` is the thread's own copy of the accessor. kLit: the shadow transmittance
+// comes from the light volume (exp(ext * tau_hat)) instead of a shadow walk; everything else,
+// the alpha channel included, is the marched mode's.
+template <bool kLit = false, typename Vol>
 __device__ __forceinline__ void vol_march_pixel(Vol& vol, const anr_camera* __restrict__ cams,
                                                 int32_t H, int32_t W, int32_t tiles_x,
                                                 int32_t tiles_y, const VolMarch& m,
@@ -118,22 +167,32 @@ __device__ __forceinline__ void vol_march_pixel(Vol& vol, const anr_camera* __re
     float p[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = cam.eye[a] + t * dir[a];
-    const float d = vol.sample(p[0], p[1], p[2]);
+    float tau_hat = 0.0f;
+    float d;
+    if constexpr (kLit)
+      d = vol.lit_sample(p[0], p[1], p[2], m.cutoff, &tau_hat);
+    else
+      d = vol.sample(p[0], p[1], p[2]);
     if (d < m.cutoff) continue;
-    // shadow ray towards the light
     float sT[3] = {1.0f, 1.0f, 1.0f};
-    float s0, s1;
-    if (vol_clip(vol.nx, vol.ny, vol.nz, p, m.light, &s0, &s1)) {
-      for (int32_t q = 1; q <= m.max_shadow; ++q) {
-        const float s = static_cast<float>(q) * m.shadow_step;
-        if (!(s <= s1)) break;
-        const float ds = vol.sample(p[0] + s * m.light[0], p[1] + s * m.light[1],
-                                    p[2] + s * m.light[2]);
-        if (ds < m.cutoff) continue;
-        const float gain = 1.0f + s * m.light_gain;
+    if constexpr (kLit) {
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) sT[ch] *= expf(m.ext[ch] * ds * m.shadow_step / gain);
-        if (sT[0] * sT[0] + sT[1] * sT[1] + sT[2] * sT[2] < m.cutoff) break;
+      for (int ch = 0; ch < 3; ++ch) sT[ch] = expf(m.ext[ch] * tau_hat);
+    } else {
+      // shadow ray towards the light
+      float s0, s1;
+      if (vol_clip(vol.nx, vol.ny, vol.nz, p, m.light, &s0, &s1)) {
+        for (int32_t q = 1; q <= m.max_shadow; ++q) {
+          const float s = static_cast<float>(q) * m.shadow_step;
+          if (!(s <= s1)) break;
+          const float ds = vol.sample(p[0] + s * m.light[0], p[1] + s * m.light[1],
+                                      p[2] + s * m.light[2]);
+          if (ds < m.cutoff) continue;
+          const float gain = 1.0f + s * m.light_gain;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) sT[ch] *= expf(m.ext[ch] * ds * m.shadow_step / gain);
+          if (sT[0] * sT[0] + sT[1] * sT[1] + sT[2] * sT[2] < m.cutoff) break;
+        }
       }
     }
 #pragma unroll

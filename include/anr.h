@@ -58,7 +58,11 @@ extern "C" {
  *   - anr_sparse_volume_coarse_words, anr_sparse_volume_mark, anr_sparse_volume_popcount,
  *     anr_sparse_volume_place, anr_sparse_volume_sample and anr_sparse_volume_render (the
  *     global-grid extract's sparse volume -- bitmap, rank and ordered values -- and the same
- *     march over it, with anr_sparse_volume).
+ *     march over it, with anr_sparse_volume);
+ *   - anr_volume_light, anr_volume_render_lit, anr_sparse_volume_light and
+ *     anr_sparse_volume_render_lit (the light volume: the shadow optical depth of every voxel,
+ *     summed once per video, and the march that interpolates it -- a second, opt-in shadow
+ *     mode beside the marched one, which is unchanged).
  * ABI 4 (r06): anr_ingp_hash_field_fwd.
  * ABI 3 (r05): anr_hashgrid_fwd_planes, and the fused field entry points' enc_stride < 0
  *   selecting the level-quad-plane layout it writes. */
@@ -664,6 +668,54 @@ int anr_sparse_volume_render(const anr_sparse_volume* volume, int32_t skip,
                              const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
                              const anr_volume_params* params, float* rgba, int64_t* counters,
                              anr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Light volume: precomputed shadows, a second shadow mode of the two marchers above
+ * (csrc/volume_march.h). The light does not move during an orbit, so the shadow optical depth
+ * of every voxel is summed once and interpolated at each primary sample. An interpolated
+ * shadow is not a marched one: this mode has its own definition, below, and its own yardstick
+ * (tests/light_volume_checks.py); the marched entries are unchanged and remain the default.
+ * Parity with vdb_render: unpinned. D(p), the slab clip, the cameras and anr_volume_params are
+ * anr_volume_render's; all arithmetic is f32, in the written order, without FMA contraction.
+ * Light volume tau: defined at every voxel v with density > 0; other voxels hold 0 and are
+ * never read. It is the marched shadow loop from p = the voxel's position, the light ray
+ * clipped to the box giving [0, s1]: for q = 1, 2, ... while s = q * shadow_step <= s1:
+ * ds = D(p + s light_dir); skipped if ds < cutoff; else tau += ds * shadow_step / (1 + s *
+ * light_gain). No early termination: tau is a plain sum and does not depend on the channels.
+ * The loop keeps the march's integer bound.
+ * Lit march: the primary loop of anr_volume_render with one change. At a sample with d >=
+ * cutoff the shadow march is replaced by: over the eight corners floor(p) + {0, 1}^3, x
+ * outermost and z innermost, the low corner first, ww = (wx_a * wy_b) * wz_c, where w_a is
+ * 1 - w for the low corner and w for the high one and w = p - floor(p); a corner takes part
+ * only if it lies inside the array (sparse: is present) and its density is > 0; num += ww *
+ * tau_c and den += ww over the corners that take part; tau_hat = den > 0 ? num / den : 0;
+ * sT[ch] = expf(ext[ch] * tau_hat). d, dT, T, the termination test and A are computed exactly
+ * as in the marched mode, so the alpha channel of a lit frame equals the marched frame's bit
+ * for bit. The corner rule depends on values, never on presence, so the sparse entries give
+ * the bits of the dense ones on the densified cube in this mode too.
+ * A tau is valid only for the density it was built from and for the same light_dir,
+ * shadow_step, light_gain and cutoff; the entries cannot check that.
+ * anr_volume_light: tau (nx, ny, nz) f32 WRITTEN, the cube's layout, every voxel (0 where the
+ * density is not > 0); one thread per voxel. anr_sparse_volume_light: tau (n_values) f32
+ * WRITTEN in value order, so the rank that finds a corner's density finds its tau; one thread
+ * per value, which finds its voxel by a binary search of the ranks; skip as in the render.
+ * Both take the whole anr_volume_params and refuse what the renders refuse in it.
+ * anr_volume_render_lit, anr_sparse_volume_render_lit: the render entries' arguments and
+ * refusals, plus tau (DEVICE, as written by the light entry of the same volume; null is
+ * refused). F * H * W = 0: ANR_OK without a launch. There is no empty build: a cube has
+ * extents >= 1 and a sparse volume n_values >= 1. None of the four allocates or synchronises.
+ * ------------------------------------------------------------------------------------ */
+int anr_volume_light(const float* density, int64_t nx, int64_t ny, int64_t nz,
+                     const anr_volume_params* params, float* tau, anr_stream_t stream);
+int anr_volume_render_lit(const float* density, const float* tau, int64_t nx, int64_t ny,
+                          int64_t nz, const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
+                          const anr_volume_params* params, float* rgba, anr_stream_t stream);
+int anr_sparse_volume_light(const anr_sparse_volume* volume, int32_t skip,
+                            const anr_volume_params* params, float* tau, anr_stream_t stream);
+int anr_sparse_volume_render_lit(const anr_sparse_volume* volume, const float* tau, int32_t skip,
+                                 const anr_camera* cameras, int64_t F, int64_t H, int64_t W,
+                                 const anr_volume_params* params, float* rgba, int64_t* counters,
+                                 anr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * NeRF path (configs/nerf.json): positional encoding (encoders.py:4-28) and the

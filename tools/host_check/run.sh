@@ -2,7 +2,7 @@
 # Host-side sanitizer run of the library's argument and descriptor logic (no GPU needed, none
 # used): the library's host code and each stand-alone program here under AddressSanitizer and
 # UBSan. field_variants.cpp walks the fused field's descriptors, sparse_volume.cpp the
-# refusals of the sparse volume's entries and of the two marchers.
+# refusals of the sparse volume's entries, of the two marchers and of the light-volume entries.
 #   bash tools/host_check/run.sh [build dir]
 set -euo pipefail
 HERE=$(cd "$(dirname "$0")" && pwd)

@@ -1,6 +1,6 @@
-// Host-only walk over the argument refusals of the sparse volume's entries and of the two
-// marchers (csrc/sparse_volume.hip, csrc/volume_render.hip, the shared plan of
-// csrc/volume_march.h), for a sanitizer build (tools/host_check/run.sh: -Xarch_host
+// Host-only walk over the argument refusals of the sparse volume's entries, of the two
+// marchers and of the four light-volume entries (csrc/sparse_volume.hip,
+// csrc/volume_render.hip, the shared plan of csrc/volume_march.h), for a sanitizer build (tools/host_check/run.sh: -Xarch_host
 // -fsanitize=address,undefined). Every call here is refused, or is empty, before any launch:
 // the pointers are fake and never dereferenced. Nothing here needs a GPU.
 #include <math.h>
@@ -147,6 +147,87 @@ int main() {
     s.row_pitch = 992;
     s.n_values = 78316315;
     CHECK(anr_sparse_volume_render(&s, 1, fake_c, 3, 16, 24, &ok, 0, 0, 0) == ANR_E_INVALID);
+    CHECK(says("null pointer"));
+  }
+
+  // the light volume: the descriptor, the parameters and the image through the four entries
+  for (const auto& b : bad) {
+    anr_sparse_volume s = v;
+    b.edit(&s);
+    CHECK(anr_sparse_volume_light(&s, 1, &ok, fake_f, 0) == ANR_E_INVALID);
+    CHECK(says("anr_sparse_volume_light") && says(b.word));
+    CHECK(anr_sparse_volume_render_lit(&s, fake_f, 1, fake_c, 3, 16, 24, &ok, fake_f, 0, 0) ==
+          ANR_E_INVALID);
+    CHECK(says("anr_sparse_volume_render_lit") && says(b.word));
+  }
+  for (const auto& b : badp) {
+    anr_volume_params p = ok;
+    b.edit(&p);
+    CHECK(anr_volume_light(fake_f, 7, 5, 6, &p, fake_f, 0) == ANR_E_INVALID);
+    CHECK(says("anr_volume_light") && says(b.word));
+    CHECK(anr_volume_render_lit(fake_f, fake_f, 7, 5, 6, fake_c, 3, 16, 24, &p, fake_f, 0) ==
+          ANR_E_INVALID);
+    CHECK(says("anr_volume_render_lit") && says(b.word));
+    CHECK(anr_sparse_volume_light(&v, 1, &p, fake_f, 0) == ANR_E_INVALID);
+    CHECK(says("anr_sparse_volume_light") && says(b.word));
+    CHECK(anr_sparse_volume_render_lit(&v, fake_f, 1, fake_c, 3, 16, 24, &p, fake_f, 0, 0) ==
+          ANR_E_INVALID);
+    CHECK(says("anr_sparse_volume_render_lit") && says(b.word));
+  }
+  for (const auto& s : shapes) {
+    CHECK(anr_sparse_volume_render_lit(&v, fake_f, 1, fake_c, s[0], s[1], s[2], &ok, fake_f, 0,
+                                       0) == ANR_E_INVALID);
+    CHECK(anr_volume_render_lit(fake_f, fake_f, 7, 5, 6, fake_c, s[0], s[1], s[2], &ok, fake_f,
+                                0) == ANR_E_INVALID);
+  }
+  // a null tau, and every other null pointer
+  CHECK(anr_volume_light(fake_f, 7, 5, 6, &ok, 0, 0) == ANR_E_INVALID && says("null pointer"));
+  CHECK(anr_volume_light(0, 7, 5, 6, &ok, fake_f, 0) == ANR_E_INVALID && says("null pointer"));
+  CHECK(anr_volume_light(fake_f, 7, 5, 6, 0, fake_f, 0) == ANR_E_INVALID && says("params"));
+  CHECK(anr_volume_light(fake_f, 7, 0, 6, &ok, fake_f, 0) == ANR_E_INVALID && says("extents"));
+  CHECK(anr_volume_light(fake_f, 1024, 1024, 512, &ok, fake_f, 0) == ANR_E_INVALID);
+  CHECK(says("anr_volume_light") && says("2^31 bytes"));
+  CHECK(anr_volume_render_lit(fake_f, 0, 7, 5, 6, fake_c, 3, 16, 24, &ok, fake_f, 0) ==
+        ANR_E_INVALID);
+  CHECK(says("anr_volume_render_lit") && says("null pointer"));
+  CHECK(anr_volume_render_lit(0, fake_f, 7, 5, 6, fake_c, 3, 16, 24, &ok, fake_f, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_volume_render_lit(fake_f, fake_f, 7, 5, 6, 0, 3, 16, 24, &ok, fake_f, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_volume_render_lit(fake_f, fake_f, 7, 5, 6, fake_c, 3, 16, 24, &ok, 0, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_volume_render_lit(fake_f, fake_f, 7, 5, 6, fake_c, 3, 16, 24, 0, fake_f, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_volume_render_lit(fake_f, fake_f, 1024, 1024, 512, fake_c, 3, 16, 24, &ok, fake_f,
+                              0) == ANR_E_INVALID);
+  CHECK(says("2^31 bytes"));
+  CHECK(anr_sparse_volume_light(&v, 1, &ok, 0, 0) == ANR_E_INVALID && says("null pointer"));
+  CHECK(anr_sparse_volume_light(0, 1, &ok, fake_f, 0) == ANR_E_INVALID);
+  CHECK(anr_sparse_volume_light(&v, 1, 0, fake_f, 0) == ANR_E_INVALID && says("params"));
+  CHECK(anr_sparse_volume_light(&v, 2, &ok, fake_f, 0) == ANR_E_INVALID && says("skip"));
+  CHECK(anr_sparse_volume_render_lit(&v, 0, 1, fake_c, 3, 16, 24, &ok, fake_f, 0, 0) ==
+        ANR_E_INVALID);
+  CHECK(says("anr_sparse_volume_render_lit") && says("null pointer"));
+  CHECK(anr_sparse_volume_render_lit(0, fake_f, 1, fake_c, 3, 16, 24, &ok, fake_f, 0, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_sparse_volume_render_lit(&v, fake_f, -1, fake_c, 3, 16, 24, &ok, fake_f, 0, 0) ==
+        ANR_E_INVALID);
+  CHECK(says("skip"));
+  CHECK(anr_sparse_volume_render_lit(&v, fake_f, 1, 0, 3, 16, 24, &ok, fake_f, 0, 0) ==
+        ANR_E_INVALID);
+  CHECK(anr_sparse_volume_render_lit(&v, fake_f, 1, fake_c, 3, 16, 24, &ok, 0, 0, 0) ==
+        ANR_E_INVALID);
+  // no pixels: ANR_OK without a launch, whatever the pointers
+  CHECK(anr_volume_render_lit(0, 0, 7, 5, 6, 0, 0, 16, 24, &ok, 0, 0) == ANR_OK);
+  CHECK(anr_volume_render_lit(0, 0, 7, 5, 6, 0, 3, 16, 0, &ok, 0, 0) == ANR_OK);
+  CHECK(anr_sparse_volume_render_lit(&v, 0, 1, 0, 0, 16, 24, &ok, 0, 0, 0) == ANR_OK);
+  CHECK(anr_sparse_volume_render_lit(&v, 0, 1, 0, 3, 0, 24, &ok, 0, 0, 0) == ANR_OK);
+  {  // skip = 0 needs no brick level: only the null tau stops the calls
+    anr_sparse_volume s = v;
+    s.coarse = nullptr;
+    CHECK(anr_sparse_volume_light(&s, 0, &ok, 0, 0) == ANR_E_INVALID && says("null pointer"));
+    CHECK(anr_sparse_volume_render_lit(&s, 0, 0, fake_c, 3, 16, 24, &ok, fake_f, 0, 0) ==
+          ANR_E_INVALID);
     CHECK(says("null pointer"));
   }
 

@@ -42,6 +42,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--light-source-color", nargs=3, type=float, default=(1.0, 1.0, 1.0), help="light colour, RGB")
     ap.add_argument("--scatter", nargs=3, type=float, default=(0.7, 0.7, 0.7), help="scattering coefficients, RGB")
     ap.add_argument("--frames-dir", default="_temp_frames", help="directory of the %%06d.ppm frames")
+    ap.add_argument("--shadows", choices=("marched", "light_volume"), default="marched", help="marched: a shadow march per sample; light_volume: shadows precomputed once per video and interpolated (another arithmetic, same alpha)")
     return ap
 
 
@@ -71,7 +72,7 @@ def main() -> None:
                                      grid_scale=args.grid_scale)
     out = make_global_video(volume, args.frames_dir, args.video_filepath, width=res[0],
                             height=res[1], duration=args.duration, frame_rate=args.frame_rate,
-                            settings=global_settings(volume, **kw))
+                            settings=global_settings(volume, **kw), shadows=args.shadows)
     out["frames"] = f"{len(out['frames'])} files under {args.frames_dir}"
     out["voxels"] = len(volume)
     print(json.dumps(out))

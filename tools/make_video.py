@@ -37,6 +37,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scatter", nargs=3, type=float, default=(0.7, 0.7, 0.7), help="scattering coefficients, RGB")
     ap.add_argument("--scene-scale", type=float, default=1000.0, help="the dataset's scale; densities are multiplied by scale / 1000")
     ap.add_argument("--frames-dir", default="_temp_frames", help="directory of the %%06d.ppm frames")
+    ap.add_argument("--shadows", choices=("marched", "light_volume"), default="marched", help="marched: a shadow march per sample; light_volume: shadows precomputed once per video and interpolated (another arithmetic, same alpha)")
     return ap
 
 
@@ -63,7 +64,7 @@ def main() -> None:
     out = make_video(args.extract_filepath, args.frames_dir, args.video_filepath,
                      band=args.render_band_idx, scene_scale=args.scene_scale, width=res[0],
                      height=res[1], duration=args.duration, frame_rate=args.frame_rate,
-                     settings=settings)
+                     settings=settings, shadows=args.shadows)
     out["frames"] = f"{len(out['frames'])} files under {args.frames_dir}"
     print(json.dumps(out))
 

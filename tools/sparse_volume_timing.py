@@ -23,6 +23,13 @@ Comparison with the dense marcher: the same scene at grid_res 0.05, whose densif
 under anr_volume_render's 2^31-byte limit. There is no vdb_render to compare with: no speed-up
 over it is claimed, and parity with it stays unpinned.
 
+Shadows: ``--shadows light_volume`` times the light-volume mode instead (SparseVolume.light
+once, anr_sparse_volume_render_lit per frame) against the marched mode in the same process at
+``--grid-res``, brick level on, the two arms alternating pose by pose (tools/
+volume_render_timing.py's shadow_modes): per-frame time of both, the light build's time, the
+break-even frame count and the RGB difference between the modes. The record goes under
+"global_grid" into ``--light-out`` (profiles/light_volume.json), beside what is already there.
+
 Registers and scratch are read from hipcc's -Rpass-analysis=kernel-resource-usage remarks for
 csrc/sparse_volume.hip when hipcc is installed.
 """
@@ -179,6 +186,34 @@ def measure(scene, grid_res, args, with_dense: bool) -> dict:
     return out
 
 
+def shadows_arm(scene, args) -> dict:
+    from atmonr_amd.sparse_volume import (global_orbit_cameras, global_settings,
+                                          render_sparse_volume)
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from volume_render_timing import shadow_modes
+
+    ds, sigma, vol, build = grid_volume(scene, args.grid_res, args.vstretch, 1)
+    settings = global_settings(vol)
+    warmup = 2
+    cams = global_orbit_cameras(vol, float(args.poses + warmup + 1), 1, W, H)[:args.poses + warmup]
+
+    def build_light():
+        vol._light = None  # a fresh build, not the kept one
+        return vol.light(settings)
+
+    out = shadow_modes(lambda c: render_sparse_volume(vol, c, W, H, settings),
+                       lambda c, light: render_sparse_volume(vol, c, W, H, settings,
+                                                             shadows="light_volume", light=light),
+                       build_light, cams, warmup)
+    out.update({"grid_res": args.grid_res, "box": list(vol.ext), "voxels": len(vol),
+                "image": [W, H], "poses": args.poses, "volume_bytes": vol.nbytes,
+                "enumeration": "one thread per value; the voxel found by a binary search of "
+                               "the ranks (the only enumeration built and measured)",
+                "settings": "global_settings: the light along the local vertical"})
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--views", type=int, default=90)
@@ -190,6 +225,8 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--build-reps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sparse_volume.json"))
+    ap.add_argument("--shadows", choices=("marched", "light_volume"), default="marched")
+    ap.add_argument("--light-out", default=os.path.join(ROOT, "profiles", "light_volume.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("sparse_volume_timing needs a GPU: nothing here can be timed without one")
@@ -197,6 +234,13 @@ def main() -> None:
 
     dev = torch.device("cuda:0")
     scene = SyntheticHARP2Dataset(n_views=args.views, img_size=args.img, device=dev)
+    if args.shadows == "light_volume":
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from volume_render_timing import merge_record
+
+        rec = shadows_arm(scene, args)
+        print(json.dumps(merge_record(args.light_out, "global_grid", rec), indent=1))
+        return
     out = {"gpu": torch.cuda.get_device_name(0), "parity_with_vdb_render": "unpinned",
            "scene": {"views": args.views, "img": args.img, "vstretch": args.vstretch,
                      "values": "the scene's extinction_truth at the voxel centres, 1/m, times the "

@@ -15,6 +15,13 @@ removed; its figures are kept in profiles/volume_render_layout_ab.json and copie
 tool's output beside the fresh one. There is no parent-commit time and no vdb_render to
 compare with: no speed-up over either is claimed.
 
+Shadows: ``--shadows light_volume`` times the light-volume mode instead (anr_volume_light once,
+anr_volume_render_lit per frame) against the marched mode in the same process, the two arms
+alternating frame by frame on the cube and cameras above: per-frame time of both, the light
+build's time, the break-even frame count (build / saving per frame), and the largest and mean
+RGB difference between the modes (alpha is asserted bit-equal). The record goes under
+"dense_cube" into ``--light-out`` (profiles/light_volume.json), beside what is already there.
+
 Lookups: D evaluations per frame, counted by the yardstick's model on a downscaled case (the
 same cloud at 64 x 10 x 64, 20 x 15 pixels, steps scaled by 1 / 8), as lookups per pixel.
 """
@@ -125,15 +132,101 @@ def timing(dev, frames: int, warmup: int) -> dict:
                           "no speed-up is claimed"}
 
 
+def _event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def _stats(xs) -> dict:
+    return {"median_ms": statistics.median(xs), "min_ms": min(xs), "max_ms": max(xs), "n": len(xs)}
+
+
+def shadow_modes(marched, lit, build, cams, warmup: int, build_reps: int = 3) -> dict:
+    """The two shadow modes frame by frame: ``marched(c)`` and ``lit(c, light)`` render the
+    cameras ``c``, ``build()`` returns a fresh light volume. Shared with
+    tools/sparse_volume_timing.py."""
+    build_ms = []
+    for rep in range(build_reps + 1):  # pass 0 warms up
+        ms, light = _event_ms(build)
+        if rep:
+            build_ms.append(ms)
+    t = {"marched": [], "light_volume": []}
+    diff_max, diff_mean = [], []
+    for f in range(cams.shape[0]):
+        tm, a = _event_ms(lambda: marched(cams[f:f + 1]))
+        tl, b = _event_ms(lambda: lit(cams[f:f + 1], light))
+        assert torch.equal(a[..., 3], b[..., 3]), f  # the alpha channel is the marched one's
+        if f >= warmup:
+            t["marched"].append(tm)
+            t["light_volume"].append(tl)
+            d = (a[..., :3] - b[..., :3]).abs()
+            diff_max.append(float(d.max()))
+            diff_mean.append(float(d.mean()))
+    out = {"ms_per_frame": {k: _stats(v) for k, v in t.items()}, "light_build_ms": _stats(build_ms),
+           "light_bytes": light.tau.numel() * light.tau.element_size(),
+           "rgb_difference_between_modes": {"largest": max(diff_max),
+                                            "mean": statistics.mean(diff_mean)},
+           "alpha_bit_equal": True, "warmup_frames": warmup}
+    saved = out["ms_per_frame"]["marched"]["median_ms"] - out["ms_per_frame"]["light_volume"]["median_ms"]
+    out["ms_saved_per_frame"] = saved
+    out["break_even_frames"] = (int(np.ceil(out["light_build_ms"]["median_ms"] / saved))
+                                if saved > 0 else None)
+    out["frames_600_ms"] = {"marched": 600 * out["ms_per_frame"]["marched"]["median_ms"],
+                            "light_volume": out["light_build_ms"]["median_ms"]
+                            + 600 * out["ms_per_frame"]["light_volume"]["median_ms"]}
+    return out
+
+
+def merge_record(path: str, key: str, rec: dict) -> dict:
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+    out.update({"gpu": torch.cuda.get_device_name(0), "parity_with_vdb_render": "unpinned",
+                key: rec})
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
+def shadows_timing(dev, frames: int, warmup: int) -> dict:
+    from atmonr_amd.video import light_volume, orbit_cameras, render_volume
+
+    nx, ny, nz, W, H = 512, 81, 512, 640, 480
+    den = cloud_cube(nx, ny, nz, device=dev)
+    n = frames + warmup
+    cams = orbit_cameras((nx, ny, nz), duration=float(n), frame_rate=1, width=W, height=H,
+                         device=dev)
+    out = shadow_modes(lambda c: render_volume(den, c, W, H),
+                       lambda c, light: render_volume(den, c, W, H, shadows="light_volume",
+                                                      light=light),
+                       lambda: light_volume(den), cams, warmup)
+    out.update({"cube": [nx, ny, nz], "image": [W, H], "settings": "defaults",
+                "nonzero_voxels": float((den > 0).float().mean())})
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "volume_render.json"))
+    ap.add_argument("--shadows", choices=("marched", "light_volume"), default="marched")
+    ap.add_argument("--light-out", default=os.path.join(ROOT, "profiles", "light_volume.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("volume_render_timing needs a GPU: nothing here can be timed without one")
     dev = torch.device("cuda:0")
+    if args.shadows == "light_volume":
+        rec = shadows_timing(dev, args.frames, args.warmup)
+        print(json.dumps(merge_record(args.light_out, "dense_cube", rec), indent=1))
+        return
     out = {"gpu": torch.cuda.get_device_name(0), "parity_with_vdb_render": "unpinned",
            "accuracy": accuracy(dev), "timing": timing(dev, args.frames, args.warmup),
            "lookups_model": lookups_model()}
